@@ -18,14 +18,18 @@ single-GPU one) inside the timed region, and rank 0 ends the step holding the wh
     rank 0 with one RCCL reduce.
 `--weak` instead renders passes [4r, 4r+4) of a (64*N)-spp frame (pass sharding; labelled "weak").
 
-After the timed region rank 0 also reports `rmse_vs_oracle`: the per-pixel RMSE of
-the developed film of a stated lane window of the same workload, HIP pipeline vs the
-CPU oracle (oracle/, a restatement of mvpath; Dr.Jit llvm_rgb cannot be built here).
+A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, the outputs
+(`--dump-outputs DIR`: the film rank 0 holds after the last timed step, as DIR/film.npy) and one JSON
+line (metric, value, unit, ms_per_step, the workload).  Everything below runs after the timed region and
+only with `--full`.
 
-The JSON line carries the dominant kernel's roofline (HIP-event timing of the
-kernel inside the timed region x its algorithmic bytes, DESIGN.md "Byte model")
-and a CPU baseline: the oracle (CPU restatement, not Dr.Jit llvm_rgb) timed on
-a bounded lane sample on this box's host cores.
+`rmse_vs_oracle`: the per-pixel RMSE of the developed film of a stated lane window of the same
+workload, HIP pipeline vs the CPU oracle (oracle/, a restatement of mvpath; Dr.Jit llvm_rgb cannot be
+built here).
+
+The dominant kernel's roofline (HIP-event timing of the kernels in one instrumented frame x their
+algorithmic bytes, DESIGN.md "Byte model") and a CPU baseline: the oracle (CPU restatement, not Dr.Jit
+llvm_rgb) timed on a bounded lane sample on this box's host cores.
 """
 import argparse
 import json
@@ -41,6 +45,7 @@ for _p in (REPO, PKG):
 
 METRIC = "Msamples/sec (whole node), 8-view 1024² 64spp; per-pixel RMSE vs llvm_rgb"
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+DUMP_MAX_BYTES = 32 << 20   # --dump-outputs: largest array written whole
 
 
 # SURVEY 8 config table.  M = the metric's workload (the default bench line); the others are
@@ -73,14 +78,14 @@ def group_size(p):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps (frames)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", choices=sorted(CONFIGS), default="M",
                     help="M: the metric's workload (default); C2, C3, C5, mesh: the other configs")
     ap.add_argument("--weak", action="store_true",
                     help="pass sharding: rank r renders its own passes of an (N x spp)-spp frame (weak scaling)")
     ap.add_argument("--rmse-lanes", type=int, default=1 << 20,
-                    help="lanes of the RMSE window (0: skip); the window starts at quilt row H/4")
+                    help="--full: lanes of the RMSE window (0: skip); the window starts at quilt row H/4")
     ap.add_argument("--res", type=int, default=None)
     ap.add_argument("--spp", type=int, default=None)
     ap.add_argument("--gx", type=int, default=None)
@@ -89,12 +94,21 @@ def main():
     ap.add_argument("--adaptive", type=int, default=None)
     ap.add_argument("--partition", choices=("auto", "lanes", "view-groups"), default="auto",
                     help="multi-GPU partition of the frame (auto: view groups when they divide among the ranks)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline duration")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: target CPU-baseline duration")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--one-stream", action="store_true",
                     help="every chunk on the render stream in the timed frames too (kernel-trace profiles: "
                          "per-kernel durations that do not overlap; the default keeps the second chunk stream)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also: one instrumented frame (per-kernel times, roofline, counters), "
+                         "the RMSE window against the CPU oracle and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the film rank 0 holds after the last timed step to DIR/film.npy (float32, H x W x C "
+                         "RGBW ImageBlock; above %d MB a fixed sample of its pixels, numpy default_rng(0))"
+                         % (DUMP_MAX_BYTES >> 20))
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     cfg = dict(CONFIGS[args.config])
     for k in ("res", "spp", "gx", "gy", "reuse", "adaptive"):
         if getattr(args, k) is not None:
@@ -229,6 +243,56 @@ def main():
     total_samples = lanes_per_pass * n_passes * args.steps if lane_sharded else samples_per_rank * world * args.steps
     value = total_samples / elapsed / 1e6
 
+    if rank == 0 and args.dump_outputs:
+        # what the last timed step left with its caller: the whole ImageBlock on rank 0
+        dump_outputs(args.dump_outputs, {"film": quilt if groups is not None else film})
+
+    head = {
+        "metric": METRIC,
+        "value": round(value, 3),
+        "unit": "Msamples/s",
+        "n_gpus": world if backend != "gloo" else torch.cuda.device_count(),
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 3),
+        "higher_is_better": True,
+        "scaling": "strong" if lane_sharded else "weak",
+        "chunk_streams": 1 if args.one_stream else "auto (up to 4 for the per-depth wavefront suffix of BVH scenes)",
+        "vs_baseline": None,
+        **({"ranks": world, "dist_backend": backend,
+            "note": "rehearsal: %d ranks share %d device(s) over gloo (host-staged collectives); a check of the "
+                    "multi-rank path, not a measurement" % (world, torch.cuda.device_count())}
+           if backend == "gloo" and world > 1 else {}),
+        "dtype": "f32",
+        "data": "synthetic (%s on a %dx%d grid sensor; no external assets)" % (
+            {"veach_grid.xml": "Veach-MIS-class scene: 4 GGX rough-conductor plates, 4 sphere lights",
+             "cbox_mesh.xml": "Cornell box of util.py:551-685 as OBJ/PLY meshes (3.6 k triangles)"}.get(
+                scene_file, "Cornell box of util.py:551-685"), p.grid_x, p.grid_y),
+        "config": {
+            "workload": "%s: %s, %d-view %dx%d per view (quilt %dx%d), %d spp%s (%d passes x %d), G=%d, sa_mis, "
+                        "adaptive %d, max_depth 8, rr_depth 5, seed 0"
+                        % (args.config, scene_file, p.n_views, cfg["res"], cfg["res"], p.film_width,
+                           p.film_height, spp, "" if lane_sharded else "/GPU", n_passes, spp_pp, G,
+                           p.adaptive),
+            "samples_per_gpu_per_step": samples_per_rank,
+            "partition": partition if lane_sharded else "pass-sharded",
+            "film_bytes_per_gpu": film_bytes,
+            "parallelism": (("view groups x%d (+ one per-row count all-gather per pass) + gather of the film "
+                             "windows to rank 0" if groups is not None else
+                             "lane bands x%d (+ one count all-gather per pass) + RCCL reduce of the RGBW "
+                             "ImageBlock") if lane_sharded else
+                            "pass-sharded x%d + RCCL reduce of the RGBW ImageBlock") % world,
+        },
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(head))
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ---- everything below: --full only
     # ---- one instrumented frame (outside the timed region): per-kernel HIP-event times + lane counters.
     # Every chunk on the render stream (AMVPT_OPT_ONE_STREAM): with the second chunk stream the kernels of
     # two chunks overlap and their event intervals would double-count the frame (the same kernels and
@@ -289,43 +353,9 @@ def main():
 
     if rank == 0:
         out = {
-            "metric": METRIC,
-            "value": round(value, 3),
-            "unit": "Msamples/s",
-            "n_gpus": world if backend != "gloo" else torch.cuda.device_count(),
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 3),
-            "higher_is_better": True,
-            "scaling": "strong" if lane_sharded else "weak",
-            "chunk_streams": 1 if args.one_stream else "auto (up to 4 for the per-depth wavefront suffix of BVH scenes)",
+            **head,
             "rmse_vs_oracle": rmse,
-            "vs_baseline": None,
-            **({"ranks": world, "dist_backend": backend,
-                "note": "rehearsal: %d ranks share %d device(s) over gloo (host-staged collectives); a check of the "
-                        "multi-rank path, not a measurement" % (world, torch.cuda.device_count())}
-               if backend == "gloo" and world > 1 else {}),
-            "dtype": "f32",
-            "data": "synthetic (%s on a %dx%d grid sensor; no external assets)" % (
-                {"veach_grid.xml": "Veach-MIS-class scene: 4 GGX rough-conductor plates, 4 sphere lights",
-                 "cbox_mesh.xml": "Cornell box of util.py:551-685 as OBJ/PLY meshes (3.6 k triangles)"}.get(
-                    scene_file, "Cornell box of util.py:551-685"), p.grid_x, p.grid_y),
-            "config": {
-                "workload": "%s: %s, %d-view %dx%d per view (quilt %dx%d), %d spp%s (%d passes x %d), G=%d, sa_mis, "
-                            "adaptive %d, max_depth 8, rr_depth 5, seed 0"
-                            % (args.config, scene_file, p.n_views, cfg["res"], cfg["res"], p.film_width,
-                               p.film_height, spp, "" if lane_sharded else "/GPU", n_passes, spp_pp, G,
-                               p.adaptive),
-                "samples_per_gpu_per_step": samples_per_rank,
-                "partition": partition if lane_sharded else "pass-sharded",
-                "film_bytes_per_gpu": film_bytes,
-                "adaptive_lanes_per_gpu_per_step": c["adaptive_lanes"],
-                "parallelism": (("view groups x%d (+ one per-row count all-gather per pass) + gather of the film "
-                                 "windows to rank 0" if groups is not None else
-                                 "lane bands x%d (+ one count all-gather per pass) + RCCL reduce of the RGBW "
-                                 "ImageBlock") if lane_sharded else
-                                "pass-sharded x%d + RCCL reduce of the RGBW ImageBlock") % world,
-            },
+            "config": dict(head["config"], adaptive_lanes_per_gpu_per_step=c["adaptive_lanes"]),
             "roofline": {
                 "bound": bound,
                 "kernel": dom,
@@ -377,6 +407,22 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(directory, tensors):
+    """--dump-outputs: each device tensor as <directory>/<name>.npy (float32).  An (H, W, C) film above
+    DUMP_MAX_BYTES is written as the (n, C) rows of a fixed pixel sample: the sorted indices
+    numpy.random.default_rng(0) draws without replacement from its H * W pixels -- the same pixels for
+    every run of the same arguments, so two builds compare pixel for pixel."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, t in tensors.items():
+        a = np.ascontiguousarray(t.detach().cpu().numpy(), dtype=np.float32)
+        if a.nbytes > DUMP_MAX_BYTES:
+            a = a.reshape(-1, a.shape[-1])
+            n = DUMP_MAX_BYTES // (a.shape[1] * a.itemsize)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], size=n, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def rmse_window(dev, sd, vd, p, plan, n, stream):

@@ -2,8 +2,9 @@
 # usage: bash tools/ab.sh <tag> <libdir> [<libdir> ...]   (dirs relative to mitsuba3-amvpt_amd/)
 set -e
 TAG=$1; shift
-mkdir -p gpurun_out
+O=${AMVPT_OUT:-out}   # output directory
+mkdir -p $O
 for L in "$@"; do
-  AMVPT_LIB_DIR=$PWD/mitsuba3-amvpt_amd/$L timeout -k 10 120 python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline > gpurun_out/${TAG}_$L.json 2> gpurun_out/${TAG}_$L.err
-  python3 -c "import json,sys; d=json.load(open('gpurun_out/${TAG}_$L.json')); print('$L', d['value'], d['roofline']['stage_ms'])"
+  AMVPT_LIB_DIR=$PWD/mitsuba3-amvpt_amd/$L timeout -k 10 120 python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $O/${TAG}_$L.json 2> $O/${TAG}_$L.err
+  python3 -c "import json,sys; d=json.load(open('$O/${TAG}_$L.json')); print('$L', d['value'], d['roofline']['stage_ms'])"
 done

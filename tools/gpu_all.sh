@@ -15,7 +15,8 @@ if [ "${AB:-1}" = 1 ]; then
 fi
 one() {   # config
   c=$1
-  if [ $c = M ]; then B="--steps 10 --warmup 2"; P=""; else B="--steps 3 --warmup 1 --no-cpu-baseline --config $c"; P="--config $c"; fi
+  # --full: the instrumented frame (two frames per --steps 1 run, as tools/pmc_*.py count) and the whole bench line
+  if [ $c = M ]; then B="--full --steps 10 --warmup 2"; P="--full"; else B="--full --steps 3 --warmup 1 --no-cpu-baseline --config $c"; P="--full --config $c"; fi
   $S 500 bench_$c -- python -u bench.py $B
   cp gpurun_out/${T}_bench_$c.log gpurun_out/${T}_bench_$c.json 2>/dev/null
   $S 300 trace_$c -- rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${T}_trace_$c -o run -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --rmse-lanes 0 --one-stream $P
@@ -26,6 +27,6 @@ one() {   # config
 one M
 one C3
 one mesh
-$S 300 bench_C5 -- python -u bench.py --config C5 --steps 3 --warmup 1 --no-cpu-baseline
+$S 300 bench_C5 -- python -u bench.py --full --config C5 --steps 3 --warmup 1 --no-cpu-baseline
 cat gpurun_out/${T}_steps.log
 echo all-done

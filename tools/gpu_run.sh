@@ -8,7 +8,8 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 S="bash tools/gpu_step.sh $T"
 for st in "$@"; do
   kind=${st%%:*}; c=${st#*:}
-  if [ "$c" = M ] || [ "$c" = "$kind" ]; then P=""; else P="--config $c"; fi
+  # --full: the instrumented frame (two frames per --steps 1 run, as tools/pmc_*.py count) and the whole bench line
+  if [ "$c" = M ] || [ "$c" = "$kind" ]; then P="--full"; else P="--full --config $c"; fi
   case $kind in
     tests) $S 900 tests -- python -u -m pytest tests -m gpu -x -v -rA --timeout 300 --timeout-method thread ;;
     testslib) $S 900 tests_$c -- env AMVPT_LIB_DIR=$GRAFT_REPO_ROOT/mitsuba3-amvpt_amd/$c python -u -m pytest tests -m gpu -x -v -rA --timeout 300 --timeout-method thread ;;

@@ -3,6 +3,7 @@
 # usage: bash tools/pmc_mem.sh <tag> [bench args...]
 set -e
 TAG=$1; shift
+set -- --full "$@"   # the timed frame and the instrumented frame, as the earlier profiles of this set
 mkdir -p gpurun_out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 A="TA_TA_BUSY TA_ADDR_STALLED_BY_TC_CYCLES TCP_TOTAL_CACHE_ACCESSES TCP_TCC_READ_REQ TCP_PENDING_STALL_CYCLES TCP_TCP_LATENCY GRBM_GUI_ACTIVE GRBM_COUNT"

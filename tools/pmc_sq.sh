@@ -3,6 +3,7 @@
 # usage: bash tools/pmc_sq.sh <tag> [bench args...]
 set -e
 TAG=$1; shift
+set -- --full "$@"   # the timed frame and the instrumented frame: the two frames tools/pmc_valu.py divides by
 mkdir -p gpurun_out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 A="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_BRANCH"
