@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define AMVPT_ABI_VERSION 10
+#define AMVPT_ABI_VERSION 11
 
 typedef enum amvpt_status {
     AMVPT_OK = 0,
@@ -394,6 +394,9 @@ enum {
                                        * mesh (no per-lane face screening); results are identical */
     AMVPT_OPT_THREADED_BVH = 128u,    /* ABI 10: the per-lane suffix walks of large BVHs take the threaded (skip-link)
                                        * tree instead of the two-box one; results are identical */
+    AMVPT_OPT_SPLIT_PRIMARY = 256u,   /* ABI 11: the primary vertex of small all-diffuse scenes as three launches
+                                       * (k_prim_hit_req, k_vis, k_mv_primary) instead of the fused k_mv_primary;
+                                       * results are identical */
     AMVPT_OPT_DETERMINISTIC = 16u     /* bitwise-reproducible film: splats summed as 32.32 fixed point with
                                        * integer atomics (order-independent), added to the film once at the
                                        * end; each footprint-cell add is rounded to a multiple of 2^-32 and

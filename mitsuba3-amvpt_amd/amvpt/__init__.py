@@ -120,6 +120,7 @@ OPT_GENERIC_KERNELS, OPT_WAVEFRONT_SUFFIX, OPT_SPLIT_NEE, OPT_ONE_STREAM, OPT_DE
 OPT_NO_BINNING = 32
 OPT_NO_BOX_SCREEN = 64
 OPT_THREADED_BVH = 128
+OPT_SPLIT_PRIMARY = 256
 
 
 def wrap_run_exchange(fn):

@@ -153,6 +153,7 @@ struct KParams {
      * the lane's virtual index in the render's lane set */
     unsigned long long *rng_in, *rng_out;
     uint32_t box_screen;  /* the brute-force suffix walks screen box meshes (box_walk); 0: AMVPT_OPT_NO_BOX_SCREEN */
+    uint32_t split_prim;  /* host only (launch_primary): AMVPT_OPT_SPLIT_PRIMARY, no fused primary vertex */
     float bin_lo[3], bin_scale[3];   /* ray binning: the scene box's low corner and cells per unit (bin_key) */
 };
 
@@ -2724,6 +2725,8 @@ AD bool occluded_n(const Bufs &B, uint32_t Gn, uint32_t i, int k) {
  *                mixture pdf) with the ray tests read from the ballots
  * k_prim_req and k_mv_primary evaluate the same functions on the same inputs, so the
  * traced rays are exactly the reference's.
+ * Sphere-free all-diffuse scenes walked wave-uniformly do not split: k_mv_primary's kFuse
+ * instance traces all three kinds of ray itself and evaluates everything once (launch_primary).
  */
 template <bool kUni>
 __global__ void __launch_bounds__(256) k_prim_hit(KParams P, const DScene *Sp, const DView *V, Bufs B) {
@@ -3064,10 +3067,15 @@ template <int G> constexpr int prim_block() { return G > 0 ? kPrimBlock : 64; } 
  * all-diffuse computation -- it reads the hit's BSDF only, so the values are the generic path's -- and
  * writes the compact records (one weight per view, vrec_compact) with LF_DIFFW in its lane flags;
  * k_splat_multi reads such a wave's records the all-diffuse way.
+ * kFuse (the fused primary vertex of sphere-free all-diffuse scenes walked wave-uniformly, see launch_primary):
+ * the lane traces its own closest hit after the raygen, and the emitter sample's shadow ray and each view's
+ * visibility ray where their verdicts are used -- the rays k_prim_hit_req would request and k_vis would trace, so
+ * nothing reads Bufs::hit / vreq / occ and every value is the split path's.
  */
-template <int G, bool kTab, bool kDiff, bool kGenRec>
+template <int G, bool kTab, bool kDiff, bool kGenRec, bool kFuse = false>
 AD void mv_primary_lane(const KParams &P, const DScene &S, const SceneRef &sc, const DView *V, const Bufs &B,
                         float *const vs, const uint32_t vs_stride, const uint32_t slot, const uint32_t i, const bool ok) {
+    static_assert(!kFuse || (kDiff && !kGenRec && G >= 2), "the fused primary vertex: all-diffuse compile-time groups");
     const int Gn = group_size<G>(P);
     constexpr bool kPdfRegs = pdf_in_regs<G, kDiff>();
     constexpr bool kJpRegs = diff_regs<G, kDiff>();   /* F_JP in registers as well: no per-view LDS state */
@@ -3079,10 +3087,13 @@ AD void mv_primary_lane(const KParams &P, const DScene &S, const SceneRef &sc, c
     if (ok) {
         /* every global load first: a load issued after the record stores would wait
          * for them (vmcnt counts loads and stores in issue order) */
-        const float4 hitv = B.hit[i];
+        float4 hitv = make_float4(0.f, 0.f, 0.f, 0.f);
         VMask<G> occm = 0;   /* bit k: k_vis found slot k occluded */
+        if constexpr (!kFuse) {
+            hitv = B.hit[i];
 #pragma unroll
-        for (int k = 0; k < Gn; ++k) mset(occm, k, occluded_n(B, (uint32_t) Gn, i, k));
+            for (int k = 0; k < Gn; ++k) mset(occm, k, occluded_n(B, (uint32_t) Gn, i, k));
+        }
         const uint32_t n = P.chunk_n;
         const PrimRay pr = primary_raygen(P, V, i);
         Pcg rng = pr.rng;
@@ -3119,7 +3130,20 @@ AD void mv_primary_lane(const KParams &P, const DScene &S, const SceneRef &sc, c
         float pdfW = 1.f;
         bool should_mis = P.sa_mis != 0;
         if (P.max_depth != 0) {
-            SI si = compute_si(sc, pray, hit_of(hitv));
+            Hit phit;
+            if constexpr (kFuse) phit = trace_closest<true, 0, 0>(sc, pray);
+            else phit = hit_of(hitv);
+            SI si = compute_si(sc, pray, phit);
+            /* slot k's ray test (0: the emitter sample's shadow ray toward `to`, k >= 1: view k's visibility ray):
+             * k_vis's ballot, or (kFuse) the same ray traced here */
+            auto occluded = [&](int k, f3 to) -> bool {
+                if constexpr (kFuse) {
+                    if (k > 0) to = camera_point(V[view_of(k)], apx, apy);
+                    return trace_any<true, 0, 0>(sc, spawn_ray_to(si.p, si.n, to));
+                } else {
+                    return mget(occm, k);
+                }
+            };
             bool p_hit = si.valid();
             hp = si.p;
             int32_t em = si_emitter(sc, si);
@@ -3132,7 +3156,7 @@ AD void mv_primary_lane(const KParams &P, const DScene &S, const SceneRef &sc, c
             float e1 = rng.next_1d(), e2 = rng.next_1d();
             DSamp ds;
             C3 em_w;
-            if (sample_emitter_direction(sc, si, e1, e2, active_em, ds, em_w) && mget(occm, 0))
+            if (sample_emitter_direction(sc, si, e1, e2, active_em, ds, em_w) && occluded(0, ds.p))
                 occlude_emitter_sample(ds, em_w);
             active_em = active_em && ds.pdf != 0.f;
             direct_l = active_em;
@@ -3209,7 +3233,7 @@ AD void mv_primary_lane(const KParams &P, const DScene &S, const SceneRef &sc, c
                     bool valid = r.valid && (r.face == p_face) && r.Jp > 0.f;
                     if (valid) {
                         ++st_vis;
-                        valid = !mget(occm, k);
+                        valid = !occluded(k, hp);
                     }
                     f3 wik = si.sh.to_local(r.d);
                     float pdf_Mat = 1.f;   /* kDiff: valid implies a diffuse hit (mat_pdf = 1) */
@@ -3452,7 +3476,7 @@ AD void mv_primary_lane(const KParams &P, const DScene &S, const SceneRef &sc, c
                     bool valid = r.valid && (r.face == p_face) && r.Jp > 0.f;
                     if (valid) {
                         ++st_vis;
-                        valid = !mget(occm, k);
+                        valid = !occluded(k, hp);
                     }
                     mset(vmask, k, valid);
                 }
@@ -3542,8 +3566,16 @@ AD bool wave_diffuse(const KParams &P, const DScene &S, const SceneRef &sc, cons
 /* kDiff: the all-diffuse scenes' kernel.  Otherwise (AMVPT_WAVE_DIFF) two launches of the generic stage:
  * kDW = true runs the waves whose primary hits are all diffuse with the all-diffuse body at its own
  * register budget (generic records), kDW = false the others with the generic body */
-template <int G, bool kTab, bool kDiff, bool kDW = false>
-__global__ void __launch_bounds__(prim_block<G>(), AMVPT_PRIM_WAVES) k_mv_primary(KParams P, const DScene *Sp, const DView *V, Bufs B) {
+#ifndef AMVPT_PRIM_FUSE_WAVES
+/* waves per SIMD the fused primary vertex's register allocation must allow (kFuse).  Measured at config M, G = 8
+ * (r07a_ab_fused_primary.log): unbounded / 5 waves 87 VGPRs, no scratch, k_mv_primary 74.0 ms per frame; 4 waves
+ * the same; 6 waves (80 VGPRs, 24 B scratch) 71.6 ms; 7 waves (72 VGPRs, 56 B) 73.9 ms; 8 waves 78.2 ms */
+#define AMVPT_PRIM_FUSE_WAVES 6
+#endif
+/* kFuse: the whole primary vertex in this launch (mv_primary_lane: closest hit, shadow and visibility rays traced
+ * in the lane); no k_prim_hit_req, no k_vis */
+template <int G, bool kTab, bool kDiff, bool kDW = false, bool kFuse = false>
+__global__ void __launch_bounds__(prim_block<G>(), kFuse ? AMVPT_PRIM_FUSE_WAVES : AMVPT_PRIM_WAVES) k_mv_primary(KParams P, const DScene *Sp, const DView *V, Bufs B) {
     constexpr int kPB = prim_block<G>();
     extern __shared__ __attribute__((aligned(16))) char lds[];
     DScene S = *Sp;
@@ -3570,7 +3602,7 @@ __global__ void __launch_bounds__(prim_block<G>(), AMVPT_PRIM_WAVES) k_mv_primar
     const uint32_t slot = ok ? lane_slot(P, i) : 0u;
 #endif
     if constexpr (kDiff) {
-        mv_primary_lane<G, kTab, true, false>(P, S, sc, V, B, vs, vs_stride, slot, i, ok);
+        mv_primary_lane<G, kTab, true, false, kFuse>(P, S, sc, V, B, vs, vs_stride, slot, i, ok);
     } else if (kDW) {
         /* the waves whose primary hits are all plain diffuse (or misses): the all-diffuse body */
         if (wave_diffuse(P, S, sc, B, i, ok)) mv_primary_lane<G, kTab, true, true>(P, S, sc, V, B, vs, vs_stride, slot, i, ok);
@@ -3807,7 +3839,7 @@ void launch_shadow(int walk, bool bin, dim3 grid, size_t lds, hipStream_t st, co
  * variant libraries) reads them once from the environment; results are identical in every setting.
  * Per-call path selection for tests goes through amvpt_render_opts.flags instead. */
 struct AbKnobs {
-    bool fuse_prim = true, row_splat = true, brute = true, fuse_nee = true, fuse_suffix = true;
+    bool fuse_prim = true, fuse_vertex = true, row_splat = true, brute = true, fuse_nee = true, fuse_suffix = true;
     uint32_t win_rs = AMVPT_WIN_RS, fused_blocks = AMVPT_FUSED_BLOCKS;
 };
 inline const AbKnobs &ab_knobs() {
@@ -3816,6 +3848,7 @@ inline const AbKnobs &ab_knobs() {
 #ifdef AMVPT_AB_KNOBS
         auto off = [](const char *n) { const char *e = std::getenv(n); return e && e[0] == '0'; };
         r.fuse_prim = !off("AMVPT_FUSE_PRIM");
+        r.fuse_vertex = !off("AMVPT_FUSE_VERTEX");
         r.row_splat = !off("AMVPT_ROW_SPLAT");
         r.brute = !off("AMVPT_BRUTE");
         r.fuse_nee = !off("AMVPT_FUSE_NEE");
@@ -3913,6 +3946,17 @@ void launch_primary(uint32_t cn, size_t lds_tab, size_t lds_bvh, hipStream_t st,
     constexpr int kPB = prim_block<G>(), kVW = vis_waves<G>();
     const dim3 g256((cn + 255) / 256), g64((cn + 63) / 64), gp((cn + kPB - 1) / kPB);
     const size_t lds_view = B.vstate ? 0u : (size_t) (diff ? vs_fields<G, true>() : vs_fields<G, false>()) * group_size_host<G>(P) * kPB * sizeof(float);
+    if constexpr (G >= 2) {
+        /* sphere-free all-diffuse scenes walked wave-uniformly, compile-time groups: the whole vertex in one launch
+         * (k_mv_primary's kFuse instance) -- the request code evaluated the functions k_mv_primary evaluates again,
+         * only to hand k_vis its rays.  AMVPT_OPT_SPLIT_PRIMARY keeps the three launches. */
+        if (uni && ab_knobs().fuse_prim && ab_knobs().fuse_vertex && !P.split_prim && tab && diff && P.sph == 0) {
+            T.begin(AMVPT_K_MV_PRIMARY, st);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mv_primary<G, true, true, false, true>), gp, dim3(kPB), lds_tab + lds_view, st, P, S, V, B);
+            T.end(st);
+            return;
+        }
+    }
     if (uni && ab_knobs().fuse_prim) {
         T.begin(AMVPT_K_PRIM_HIT, st);
         /* sphere-free scenes: the instances without float64 sphere code (the Cornell and mesh benches); scenes of
@@ -4432,6 +4476,7 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
     P.adapt_w = 1.f / (float) (n_adapt + 1);
     P.trav_mode = trav;
     P.box_screen = (opts.flags & AMVPT_OPT_NO_BOX_SCREEN) ? 0u : 1u;
+    P.split_prim = (opts.flags & AMVPT_OPT_SPLIT_PRIMARY) ? 1u : 0u;
     for (int a = 0; a < 3; ++a) {
         const float ext = scene->root_hi[a] - scene->root_lo[a];
         P.bin_lo[a] = scene->root_lo[a];
