@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define AMVPT_ABI_VERSION 11
+#define AMVPT_ABI_VERSION 12
 
 typedef enum amvpt_status {
     AMVPT_OK = 0,
@@ -143,7 +143,15 @@ typedef struct amvpt_view_desc {
 /* ------------------------------------------------------------------ */
 
 enum { AMVPT_INTEGRATOR_MVPATH = 0, AMVPT_INTEGRATOR_PATH = 1 };
-enum { AMVPT_RFILTER_BOX = 0, AMVPT_RFILTER_GAUSSIAN = 1 };
+enum {
+    AMVPT_RFILTER_BOX = 0,        /* src/rfilters/box.cpp        */
+    AMVPT_RFILTER_GAUSSIAN = 1,   /* src/rfilters/gaussian.cpp   */
+    /* ABI 12 */
+    AMVPT_RFILTER_TENT = 2,       /* src/rfilters/tent.cpp       */
+    AMVPT_RFILTER_MITCHELL = 3,   /* src/rfilters/mitchell.cpp   */
+    AMVPT_RFILTER_CATMULLROM = 4, /* src/rfilters/catmullrom.cpp */
+    AMVPT_RFILTER_LANCZOS = 5     /* src/rfilters/lanczos.cpp    */
+};
 
 typedef struct amvpt_params {
     uint32_t integrator;     /* AMVPT_INTEGRATOR_* */
@@ -184,6 +192,12 @@ typedef struct amvpt_params {
      * quilt tile pitch of reprojected views is film->size() / grid, mvpath_multi.h:62).  Zeros: no crop. */
     uint32_t crop_offset_x, crop_offset_y;
     uint32_t full_width, full_height;
+    /* ABI 12: the other reconstruction filters' parameters (0 = the reference's default).  rfilter_radius: the tent's
+     * `radius` (default 1) or Lanczos' integer `lobes` as a float (default 3), ignored by the other filters;
+     * rfilter_b / rfilter_c: Mitchell-Netravali's B and C as given (the host loader fills the default 1/3; they have
+     * no "unset" value, 0 is a legal B or C) */
+    float rfilter_radius;
+    float rfilter_b, rfilter_c;
 } amvpt_params;
 
 /* Per-render counters (device-side lane statistics; SURVEY 8(d) byte model). */
@@ -256,6 +270,11 @@ amvpt_status amvpt_scene_stats(const amvpt_scene *scene, uint32_t *n_nodes, uint
  * or any 12-triangle mesh tiling the faces of a parallelepiped; used by the brute-force walks of scenes of at
  * most 48 primitives, DESIGN.md "Box meshes") */
 amvpt_status amvpt_scene_desc_boxes(const amvpt_scene_desc *d, uint32_t *n_boxes);
+
+/* ABI 12, host only (no device needed): the reconstruction filter of `params` at the n arguments x[] -- the
+ * function the splat kernels evaluate, compiled for the host -- and its radius (radius may be NULL).  Every
+ * AMVPT_RFILTER_* value; an rfilter above AMVPT_RFILTER_LANCZOS is AMVPT_ERR_INVALID (amvpt_render* refuses it too). */
+amvpt_status amvpt_rfilter_eval(const amvpt_params *params, const float *x, uint32_t n, float *out, float *radius);
 
 /* Number of channels of the ImageBlock (4 = RGBW, 5 = RGBAW). */
 uint32_t amvpt_film_channels(const amvpt_params *params);
@@ -397,6 +416,9 @@ enum {
     AMVPT_OPT_SPLIT_PRIMARY = 256u,   /* ABI 11: the primary vertex of small all-diffuse scenes as three launches
                                        * (k_prim_hit_req, k_vis, k_mv_primary) instead of the fused k_mv_primary;
                                        * results are identical */
+    AMVPT_OPT_BLOCK_SPLAT = 512u,     /* ABI 12: the splat takes the per-lane block window even where the row-reduced
+                                       * splat is eligible (every filter, the default Gaussian included); results are
+                                       * identical up to float summation order */
     AMVPT_OPT_DETERMINISTIC = 16u     /* bitwise-reproducible film: splats summed as 32.32 fixed point with
                                        * integer atomics (order-independent), added to the film once at the
                                        * end; each footprint-cell add is rounded to a multiple of 2^-32 and

@@ -67,7 +67,9 @@ class Params(ctypes.Structure):
         "debug", "adaptive", "spp_pass_lim", "reuse_count", "spp", "seed", "base_seed", "n_views",
         "multisensor", "grid_x", "grid_y", "reverse_x", "reverse_y", "film_width", "film_height",
         "film_alpha", "rfilter")] + [("rfilter_stddev", f32), ("batch", u32), ("crop_offset_x", u32),
-                                      ("crop_offset_y", u32), ("full_width", u32), ("full_height", u32)]
+                                      ("crop_offset_y", u32), ("full_width", u32), ("full_height", u32),
+                                      # ABI 12: tent radius / Lanczos lobes (0: default), Mitchell's B and C
+                                      ("rfilter_radius", f32), ("rfilter_b", f32), ("rfilter_c", f32)]
 
 
 class Counters(ctypes.Structure):
@@ -121,6 +123,10 @@ OPT_NO_BINNING = 32
 OPT_NO_BOX_SCREEN = 64
 OPT_THREADED_BVH = 128
 OPT_SPLIT_PRIMARY = 256
+OPT_BLOCK_SPLAT = 512   # ABI 12: the per-lane block-window splat even where the row-reduced one is eligible
+
+# amvpt_params.rfilter
+RFILTER_BOX, RFILTER_GAUSSIAN, RFILTER_TENT, RFILTER_MITCHELL, RFILTER_CATMULLROM, RFILTER_LANCZOS = range(6)
 
 
 def wrap_run_exchange(fn):
@@ -190,6 +196,10 @@ def hip_lib():
         if hasattr(L, "amvpt_release_device_memory"):
             L.amvpt_release_device_memory.argtypes = [ctypes.c_int]
         L.amvpt_device_count.argtypes = [ctypes.POINTER(ctypes.c_int)]
+        if hasattr(L, "amvpt_rfilter_eval"):
+            L.amvpt_rfilter_eval.restype = ctypes.c_int
+            L.amvpt_rfilter_eval.argtypes = [ctypes.POINTER(Params), ctypes.c_void_p, u32, ctypes.c_void_p,
+                                             ctypes.POINTER(f32)]
         _hip = L
     return _hip
 
@@ -281,6 +291,20 @@ class Scene:
         _check(self._lib.amvpt_host_describe(self._h, sensor, seed, spp, ctypes.byref(sd), ctypes.byref(vd),
                                              ctypes.byref(p)), self._lib)
         return sd, vd, p
+
+
+def rfilter_eval(params, xs):
+    """(values, radius) of the reconstruction filter of `params` at the float32 arguments `xs`: the function the
+    splat kernels evaluate, compiled for the host (amvpt_rfilter_eval; needs no device)."""
+    import numpy as np
+    L = hip_lib()
+    x = np.ascontiguousarray(xs, dtype=np.float32).ravel()
+    out = np.empty_like(x)
+    radius = f32()
+    rc = L.amvpt_rfilter_eval(ctypes.byref(params), x.ctypes.data, x.size, out.ctypes.data, ctypes.byref(radius))
+    if rc != 0:
+        raise RuntimeError(L.amvpt_last_error().decode())
+    return out.reshape(np.shape(xs)), radius.value
 
 
 def load_file(path, **defines):

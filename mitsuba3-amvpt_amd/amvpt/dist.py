@@ -129,13 +129,22 @@ FILTER_BORDER = 4   # the smallest border: the default Gaussian (radius 2) with 
 def filter_border(params):
     """Pixels around a rank's tiles its splats can reach (host/multi.cpp filter_border): ImageBlock::put's
     footprint reaches ceil(radius - 1/2) cells coalesced, ceil(radius + 1/2) not coalesced, radius = 4
-    stddev (gaussian.cpp:48-60); the box filter stays in its pixel.  At least FILTER_BORDER."""
+    stddev (gaussian.cpp:48-60), the tent's radius, 2 for Mitchell and Catmull-Rom, the lobes for Lanczos; the
+    box filter stays in its pixel.  At least FILTER_BORDER."""
     import math
     import numpy as np
-    if params.rfilter == 0:   # AMVPT_RFILTER_BOX
+    kind = params.rfilter
+    if kind == 0:   # AMVPT_RFILTER_BOX
         return FILTER_BORDER
-    stddev = params.rfilter_stddev if params.rfilter_stddev > 0 else 0.5
-    radius = float(np.float32(4.0) * np.float32(stddev))
+    if kind == 2:   # AMVPT_RFILTER_TENT
+        radius = params.rfilter_radius if params.rfilter_radius > 0 else 1.0
+    elif kind in (3, 4):   # AMVPT_RFILTER_MITCHELL, AMVPT_RFILTER_CATMULLROM
+        radius = 2.0
+    elif kind == 5:   # AMVPT_RFILTER_LANCZOS
+        radius = params.rfilter_radius if params.rfilter_radius > 0 else 3.0
+    else:
+        stddev = params.rfilter_stddev if params.rfilter_stddev > 0 else 0.5
+        radius = float(np.float32(4.0) * np.float32(stddev))
     return max(FILTER_BORDER, int(math.ceil(np.float32(radius) + np.float32(0.5))))
 
 

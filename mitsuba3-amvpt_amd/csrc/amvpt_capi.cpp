@@ -305,6 +305,10 @@ amvpt_status amvpt_set_device(int device) {
 
 uint32_t amvpt_film_channels(const amvpt_params *p) { return p && p->film_alpha ? 5u : 4u; }
 
+amvpt_status amvpt_rfilter_eval(const amvpt_params *params, const float *x, uint32_t n, float *out, float *radius) {
+    return rfilter_eval_impl(params, x, n, out, radius);
+}
+
 amvpt_status amvpt_set_chunk_lanes(uint64_t chunk_lanes) {
     g_chunk_lanes = chunk_lanes ? std::max<uint64_t>(256, chunk_lanes) : 0;   /* 0: automatic */
     return AMVPT_OK;

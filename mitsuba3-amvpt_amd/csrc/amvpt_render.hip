@@ -155,6 +155,7 @@ struct KParams {
     uint32_t box_screen;  /* the brute-force suffix walks screen box meshes (box_walk); 0: AMVPT_OPT_NO_BOX_SCREEN */
     uint32_t split_prim;  /* host only (launch_primary): AMVPT_OPT_SPLIT_PRIMARY, no fused primary vertex */
     float bin_lo[3], bin_scale[3];   /* ray binning: the scene box's low corner and cells per unit (bin_key) */
+    uint32_t filt_kind;   /* FILT_* of `filt` (dmath.h): what the FK_ANY splat instances evaluate */
 };
 
 /* the PCG32 a stock-path lane starts the pass with: TEA-seeded, or the previous pass's state (same
@@ -908,6 +909,21 @@ template <int C> AD void splat_lds_init(SplatLds<C> &L) {
 
 struct Foot { int x0, y0, nx, ny; float rx, ry; bool ok; };
 
+/*
+ * Filter form of a splat instance (template argument kF).  FK_LEGACY: the box filter and the Gaussian, as every
+ * instance evaluated them before the other filters existed (P.box, gaussian_eval; the row splat with
+ * default_filter()'s literals) -- these instances take no filter kind at run time.  FK_ANY: any filter by the
+ * kernel-uniform P.filt_kind (per-lane block window, direct puts).  FK_TENT / FK_MITCHELL / FK_CATMULLROM: the row
+ * splat of the filter at its default parameters, scalars as literals (filter_eval_lit).
+ */
+enum : int { FK_LEGACY = 0, FK_ANY = 1, FK_TENT = (int) FILT_TENT, FK_MITCHELL = (int) FILT_MITCHELL, FK_CATMULLROM = (int) FILT_CATMULLROM };
+/* the filter at x of a non-box render (callers test P.box first) */
+template <int kF> AD float feval(const KParams &P, float x) {
+    if constexpr (kF == FK_LEGACY) return gaussian_eval(P.filt, x);
+    else if constexpr (kF == FK_ANY) return filter_eval(P.filt_kind, P.filt, x);
+    else return filter_eval_lit<(uint32_t) kF>(x);
+}
+
 /* Footprint of ImageBlock::put: first covered pixel (x0, y0), extent (nx, ny) after
  * clipping, and the filter argument rx/ry of pixel (x0, y0). */
 AD Foot footprint(const KParams &P, float px, float py, bool coalesce) {
@@ -1080,7 +1096,7 @@ AD void window_flush(const KParams &P, float *film, SplatLds<C> &L, const Win &w
 /* one footprint's cells straight into the window (or the film when it does not fit) */
 /* kRolled: the window loop is not unrolled (row_put's rare per-lane path: an unrolled 5 x 5 x C
  * body would set the register allocation of the whole splat kernel) */
-template <int C, bool kRolled = false, bool kWin = true, bool kDet = true>
+template <int C, bool kRolled = false, bool kWin = true, bool kDet = true, int kF = FK_LEGACY>
 AD void foot_add(const KParams &P, float *film, WinT *const wbase, const Win &wn, const Foot &f, const float *wx,
                  const float *wy, const float *vals, bool coalesce, uint32_t *fallback) {
     const int cx0 = max(f.x0, 0), cy0 = max(f.y0, 0);
@@ -1113,11 +1129,11 @@ AD void foot_add(const KParams &P, float *film, WinT *const wbase, const Win &wn
         for (int ys = 0; ys < f.ny; ++ys) {
             const int y = f.y0 + ys;
             if (y < 0) continue;
-            const float wyv = ys < kMaxFoot ? wy[ys] : (P.box ? 1.f : gaussian_eval(P.filt, f.ry + (float) ys));
+            const float wyv = ys < kMaxFoot ? wy[ys] : (P.box ? 1.f : feval<kF>(P, f.ry + (float) ys));
             for (int xs = 0; xs < f.nx; ++xs) {
                 const int x = f.x0 + xs;
                 if (x < 0) continue;
-                const float wxv = xs < kMaxFoot ? wx[xs] : (P.box ? 1.f : gaussian_eval(P.filt, f.rx + (float) xs));
+                const float wxv = xs < kMaxFoot ? wx[xs] : (P.box ? 1.f : feval<kF>(P, f.rx + (float) xs));
                 const float w = wxv * wyv;
 #pragma unroll
                 for (int k = 0; k < C; ++k) film_cell_add<kWin, kDet>(P, film, x, y, k, P.box ? vals[k] : vals[k] * w);
@@ -1131,7 +1147,7 @@ AD void foot_add(const KParams &P, float *film, WinT *const wbase, const Win &wn
  * value * (wx * wy) per cell as ImageBlock::put forms it (imageblock.cpp:265-558) -- no LDS window and
  * no row reduction, so no float sum depends on which lanes share a wave, a chunk or a stream.
  */
-template <int C, bool kWin = true>
+template <int C, bool kWin = true, int kF = FK_LEGACY>
 AD void direct_put(const KParams &P, float *film, float px, float py, const float *vals, bool valid, bool coalesce) {
     if (!valid) return;
     const Foot f = footprint(P, px, py, coalesce);
@@ -1139,22 +1155,22 @@ AD void direct_put(const KParams &P, float *film, float px, float py, const floa
     for (int ys = 0; ys < f.ny; ++ys) {
         const int y = f.y0 + ys;
         if (y < 0) continue;
-        const float wyv = P.box ? 1.f : gaussian_eval(P.filt, f.ry + (float) ys);
+        const float wyv = P.box ? 1.f : feval<kF>(P, f.ry + (float) ys);
         for (int xs = 0; xs < f.nx; ++xs) {
             const int x = f.x0 + xs;
             if (x < 0) continue;
-            const float w = (P.box ? 1.f : gaussian_eval(P.filt, f.rx + (float) xs)) * wyv;
+            const float w = (P.box ? 1.f : feval<kF>(P, f.rx + (float) xs)) * wyv;
 #pragma unroll
             for (int k = 0; k < C; ++k) film_cell_add<kWin>(P, film, x, y, k, P.box ? vals[k] : vals[k] * w);
         }
     }
 }
 
-AD void foot_weights(const KParams &P, const Foot &f, float *wx, float *wy) {
+template <int kF = FK_LEGACY> AD void foot_weights(const KParams &P, const Foot &f, float *wx, float *wy) {
 #pragma unroll
     for (int t = 0; t < kMaxFoot; ++t) {
-        wx[t] = P.box || (AMVPT_ATTR_SKIP & 4) ? 1.f : gaussian_eval(P.filt, f.rx + (float) t);
-        wy[t] = P.box || (AMVPT_ATTR_SKIP & 4) ? 1.f : gaussian_eval(P.filt, f.ry + (float) t);
+        wx[t] = P.box || (AMVPT_ATTR_SKIP & 4) ? 1.f : feval<kF>(P, f.rx + (float) t);
+        wy[t] = P.box || (AMVPT_ATTR_SKIP & 4) ? 1.f : feval<kF>(P, f.ry + (float) t);
     }
 }
 
@@ -1192,8 +1208,10 @@ AD int row_max(int v) {
 }
 /* filter weight of film cell `cell` for a footprint starting at x0 with argument r, zero outside
  * the footprint's cells [lo, hi) -- inside it eval(r + (cell - x0)), the reference's argument */
-AD float union_weight(const FilterCoeffs &F, float r, int x0, int cell, int lo, int hi) {
-    const float w = gaussian_eval(F, r + (float) (cell - x0));
+template <int kF = FK_LEGACY> AD float union_weight(const FilterCoeffs &F, float r, int x0, int cell, int lo, int hi) {
+    float w;
+    if constexpr (kF == FK_LEGACY) w = gaussian_eval(F, r + (float) (cell - x0));
+    else w = filter_eval_lit<(uint32_t) kF>(r + (float) (cell - x0));
     return (cell >= lo && cell < hi) ? w : 0.f;
 }
 #ifndef AMVPT_SPLAT_PKW
@@ -1207,8 +1225,9 @@ AD f2v_t union_weight2(const FilterCoeffs &F, float r, int x0, int a, int b, int
     const f2v_t w = gaussian_eval2(F, f2v_t{r + (float) (a - x0), r + (float) (b - x0)});
     return f2v_t{(a >= lo && a < hi) ? w.x : 0.f, (b >= lo && b < hi) ? w.y : 0.f};
 }
-/* The row splat runs for the default Gaussian only (rfilter stddev 0.5, the reference's default,
- * gaussian.cpp): its coefficients -- exactly what gaussian_coeffs(0.5) computes on the host, checked
+/* The FK_LEGACY row splat runs for the default Gaussian only (rfilter stddev 0.5, the reference's default,
+ * gaussian.cpp; the tent, Mitchell and Catmull-Rom row instances hold their defaults' scalars the same way,
+ * filter_eval_lit): its coefficients -- exactly what gaussian_coeffs(0.5) computes on the host, checked
  * there bit for bit before the row splat is chosen -- are compile-time literals, so every Estrin step is
  * one v_fmaak/v_fma with a literal instead of two SGPR operands copied through VGPRs (gfx9 VOP3 reads one
  * SGPR per instruction), and the kernel keeps 11 fewer SGPRs live */
@@ -1232,7 +1251,7 @@ AD RowBox row_box(const Foot &f, bool act) {
     return RowBox{row_min(act ? max(f.x0, 0) : kBig), row_min(act ? max(f.y0, 0) : kBig),
                   row_max(act ? f.x0 + f.nx : -kBig), row_max(act ? f.y0 + f.ny : -kBig)};
 }
-template <int C, bool kWin = true>
+template <int C, bool kWin = true, int kF = FK_LEGACY>
 AD void row_put_win(const KParams &P, float *film, WinT *const wbase, const Win &wn, const Foot &f, bool act,
                     const float *vals, bool coalesce, uint32_t *fallback, const RowBox &ub) {
     const int x0c = max(f.x0, 0), y0c = max(f.y0, 0), x1 = f.x0 + f.nx, y1 = f.y0 + f.ny;
@@ -1285,9 +1304,9 @@ AD void row_put_win(const KParams &P, float *film, WinT *const wbase, const Win 
         if (u5) wx[5] = 0.f;
 #else
 #pragma unroll
-        for (int c = 0; c < 5; ++c) wx[c] = union_weight(F, f.rx, f.x0, ux0 + c, x0c, x1);
+        for (int c = 0; c < 5; ++c) wx[c] = union_weight<kF>(F, f.rx, f.x0, ux0 + c, x0c, x1);
         wx[5] = 0.f;
-        if (!u5) wx[5] = union_weight(F, f.rx, f.x0, ux0 + 5, x0c, x1);
+        if (!u5) wx[5] = union_weight<kF>(F, f.rx, f.x0, ux0 + 5, x0c, x1);
 #endif
         WinT *const wch = wbase + ch * wn.plane;
 #pragma unroll
@@ -1299,9 +1318,9 @@ AD void row_put_win(const KParams &P, float *film, WinT *const wbase, const Win 
             const f2v_t wyAB = union_weight2(F, f.ry, f.y0, uy0 + r, uy0 + r + 3, y0c, y1);
             const float wyA = wyAB.x, wyB = (r < 2 || !u5r) ? wyAB.y : 0.f;
 #else
-            const float wyA = union_weight(F, f.ry, f.y0, uy0 + r, y0c, y1);
+            const float wyA = union_weight<kF>(F, f.ry, f.y0, uy0 + r, y0c, y1);
             float wyB = 0.f;
-            if (r < 2 || !u5r) wyB = union_weight(F, f.ry, f.y0, uy0 + r + 3, y0c, y1);
+            if (r < 2 || !u5r) wyB = union_weight<kF>(F, f.ry, f.y0, uy0 + r + 3, y0c, y1);
 #endif
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
@@ -1356,8 +1375,8 @@ AD void row_put_win(const KParams &P, float *film, WinT *const wbase, const Win 
         }
     } else if (act) {
         float wx[kMaxFoot], wy[kMaxFoot];
-        foot_weights(P, f, wx, wy);
-        foot_add<C, true, kWin, false>(P, film, wbase, wn, f, wx, wy, vals, coalesce, fallback);
+        foot_weights<kF>(P, f, wx, wy);
+        foot_add<C, true, kWin, false, kF>(P, film, wbase, wn, f, wx, wy, vals, coalesce, fallback);
     }
 }
 
@@ -1406,7 +1425,7 @@ AD void wave_flush(const KParams &P, float *film, WinT *win, const Win &w) {
 }
 
 /* ImageBlock::put of a wave's samples through its own window (AMVPT_WAVE_WIN, row_splat) */
-template <int C, bool kWin = true>
+template <int C, bool kWin = true, int kF = FK_LEGACY>
 AD void wave_put(const KParams &P, float *film, WaveLds<C> &L, float px, float py, const float *vals, bool valid,
                  bool coalesce, uint32_t *fallback) {
     Foot f;
@@ -1442,7 +1461,7 @@ AD void wave_put(const KParams &P, float *film, WaveLds<C> &L, float px, float p
     }
     WinT *const win = L.win + (threadIdx.x >> 6) * (kWavePlane * C);
     /* row_put reads the window through L.win: hand it this wave's window */
-    row_put_win<C, kWin>(P, film, win, wn, f, act, vals, coalesce, fallback, ub);
+    row_put_win<C, kWin, kF>(P, film, win, wn, f, act, vals, coalesce, fallback, ub);
     wave_flush<C, kWin>(P, film, win, wn);
 }
 
@@ -1452,7 +1471,7 @@ AD void wave_put(const KParams &P, float *film, WaveLds<C> &L, float px, float p
  * coalesced footprint may start left/above the film).  Weight of a cell =
  * eval(rx + xs) * eval(ry + ys).  `coalesce` is uniform over the block.
  */
-template <int C>
+template <int C, int kF = FK_LEGACY>
 AD void block_put(const KParams &P, float *film, SplatLds<C> &L, int buf, float px, float py, const float *vals,
                   bool valid, bool coalesce, uint32_t *fallback = nullptr) {
     Foot f;
@@ -1462,12 +1481,13 @@ AD void block_put(const KParams &P, float *film, SplatLds<C> &L, int buf, float 
     const bool act = valid && f.ok;
     const Win wn = window_bbox(L, buf, act, max(f.x0, 0), max(f.y0, 0), f.x0 + f.nx, f.y0 + f.ny, (int) P.win_rs,
                                P.row_splat != 0);
-    if (C == 4 && P.row_splat) {
-        row_put_win<C>(P, film, L.win, wn, f, act, vals, coalesce, fallback, row_box(f, act));
+    /* (the row-reduced put inside the block window: the default Gaussian's only) */
+    if (kF == FK_LEGACY && C == 4 && P.row_splat) {
+        if constexpr (kF == FK_LEGACY) row_put_win<C>(P, film, L.win, wn, f, act, vals, coalesce, fallback, row_box(f, act));
     } else if (act) {
         float wx[kMaxFoot], wy[kMaxFoot];
-        foot_weights(P, f, wx, wy);
-        foot_add<C>(P, film, L.win, wn, f, wx, wy, vals, coalesce, fallback);
+        foot_weights<kF>(P, f, wx, wy);
+        foot_add<C, false, true, true, kF>(P, film, L.win, wn, f, wx, wy, vals, coalesce, fallback);
     }
     window_flush<C>(P, film, L, wn);
 }
@@ -2550,7 +2570,8 @@ __global__ void __launch_bounds__(kFusedBlock, kDiff ? AMVPT_FUSED_WAVES : AMVPT
 /* k_splat_single: ImageBlock::put of render_sample                    */
 /* ------------------------------------------------------------------ */
 
-template <int C>
+/* kF: the instance's filter form (FK_LEGACY: box / Gaussian; FK_ANY: the other filters, by P.filt_kind) */
+template <int C, int kF = FK_LEGACY>
 __global__ void __launch_bounds__(kSplatBlock) k_splat_single(KParams P, Bufs B) {
     __shared__ SplatLds<C> L;
     splat_lds_init(L);
@@ -2580,12 +2601,12 @@ __global__ void __launch_bounds__(kSplatBlock) k_splat_single(KParams P, Bufs B)
     }
     unsigned long long nonfinite = 0, negative = 0;
     check_sample(P, vals, ok, nonfinite, negative);
-    if (P.film_fx) direct_put<C>(P, B.film, putx, puty, vals, ok, P.coalesce_single != 0);
-    else block_put<C>(P, B.film, L, 0, putx, puty, vals, ok, P.coalesce_single != 0);
+    if (P.film_fx) direct_put<C, true, kF>(P, B.film, putx, puty, vals, ok, P.coalesce_single != 0);
+    else block_put<C, kF>(P, B.film, L, 0, putx, puty, vals, ok, P.coalesce_single != 0);
     if (B.stats) { stat_add(B.stats, 6, nonfinite); stat_add(B.stats, 7, negative); }
 }
 
-template <int C>
+template <int C, int kF = FK_LEGACY>
 __global__ void __launch_bounds__(kSplatBlock) k_splat_adapt(KParams P, Bufs B) {
     __shared__ SplatLds<C> L;
     splat_lds_init(L);
@@ -2603,8 +2624,8 @@ __global__ void __launch_bounds__(kSplatBlock) k_splat_adapt(KParams P, Bufs B) 
     }
     unsigned long long nonfinite = 0, negative = 0;
     check_sample(P, vals, ok, nonfinite, negative);
-    if (P.film_fx) direct_put<C>(P, B.film, sx, sy, vals, ok, false);
-    else block_put<C>(P, B.film, L, 0, sx, sy, vals, ok, false);
+    if (P.film_fx) direct_put<C, true, kF>(P, B.film, sx, sy, vals, ok, false);
+    else block_put<C, kF>(P, B.film, L, 0, sx, sy, vals, ok, false);
     if (B.stats) { stat_add(B.stats, 6, nonfinite); stat_add(B.stats, 7, negative); }
 }
 
@@ -3633,7 +3654,10 @@ __global__ void __launch_bounds__(prim_block<G>(), kFuse ? AMVPT_PRIM_FUSE_WAVES
  * kWin = false (kRow only): the film is the whole quilt */
 /* kRec = false: an instance without the record and debug paths (the bench's and every plain render's
  * row splat; 96 -> 95 VGPRs, no scratch, a third less code) */
-template <int G, int C, bool kDiff, bool kRow, bool kWin = true, bool kRec = true>
+/* kF: the instance's filter form (FK_LEGACY: box / Gaussian, the row splat with the default Gaussian's literals;
+ * FK_ANY: the other filters on the block window and the direct puts; FK_TENT / FK_MITCHELL / FK_CATMULLROM: their
+ * row splat, plain renders only) */
+template <int G, int C, bool kDiff, bool kRow, bool kWin = true, bool kRec = true, int kF = FK_LEGACY>
 __global__ void __launch_bounds__(kSplatBlock, AMVPT_SPLAT_WAVES) k_splat_multi(KParams P, const DView *V, Bufs B) {
     const bool rec_ = kRec && P.record != 0, dbg_ = kRec && P.debug != 0;
     __shared__ typename std::conditional<kRow, WaveLds<C>, SplatLds<C>>::type L;
@@ -3642,11 +3666,11 @@ __global__ void __launch_bounds__(kSplatBlock, AMVPT_SPLAT_WAVES) k_splat_multi(
     /* one put of this kernel's kind */
     auto put = [&](float x, float y, const float *vals, bool valid, bool coalesce, int buf, uint32_t *fb) {
         if constexpr (kRow) {
-            wave_put<C, kWin>(P, B.film, L, x, y, vals, valid, coalesce, fb);
+            wave_put<C, kWin, kF>(P, B.film, L, x, y, vals, valid, coalesce, fb);
         } else {
             /* deterministic mode runs these instances only (launch_splat) */
-            if (P.film_fx) direct_put<C, kWin>(P, B.film, x, y, vals, valid, coalesce);
-            else block_put<C>(P, B.film, L, buf, x, y, vals, valid, coalesce, fb);
+            if (P.film_fx) direct_put<C, kWin, kF>(P, B.film, x, y, vals, valid, coalesce);
+            else block_put<C, kF>(P, B.film, L, buf, x, y, vals, valid, coalesce, fb);
         }
     };
     const uint32_t slot = blockIdx.x * kSplatBlock + threadIdx.x;
@@ -4008,6 +4032,23 @@ template <int G>
 void launch_splat(dim3 grid, hipStream_t st, const KParams &P, const DView *V, const Bufs &B, bool diff) {
     const bool row = AMVPT_WAVE_WIN && P.row_splat && P.C == 4 && !P.film_fx;   /* deterministic: direct puts */
     const bool whole = P.fx0 == 0u && P.fy0 == 0u && P.fw == P.W && P.fh == P.H;
+    if (P.filt_kind > FILT_GAUSSIAN) {
+        /* tent, Mitchell, Catmull-Rom, Lanczos: the row splat of a plain render (render_impl sets row_splat for the
+         * filters and parameters that have one), else the block window by the filter's kind */
+        const bool plain_row = row && whole && !P.record && !P.debug;
+#define AMVPT_ROW_F(KF_)                                                                                                 \
+        if (diff) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_multi<G, 4, true, true, false, false, KF_>), grid, dim3(kSplatBlock), 0, st, P, V, B); \
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_multi<G, 4, false, true, false, false, KF_>), grid, dim3(kSplatBlock), 0, st, P, V, B);
+        if (plain_row && P.filt_kind == FILT_TENT) { AMVPT_ROW_F(FK_TENT) }
+        else if (plain_row && P.filt_kind == FILT_MITCHELL) { AMVPT_ROW_F(FK_MITCHELL) }
+        else if (plain_row && P.filt_kind == FILT_CATMULLROM) { AMVPT_ROW_F(FK_CATMULLROM) }
+#undef AMVPT_ROW_F
+        else if (P.C == 5 && diff) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_multi<G, 5, true, false, true, true, FK_ANY>), grid, dim3(kSplatBlock), 0, st, P, V, B);
+        else if (P.C == 5) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_multi<G, 5, false, false, true, true, FK_ANY>), grid, dim3(kSplatBlock), 0, st, P, V, B);
+        else if (diff) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_multi<G, 4, true, false, true, true, FK_ANY>), grid, dim3(kSplatBlock), 0, st, P, V, B);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_multi<G, 4, false, false, true, true, FK_ANY>), grid, dim3(kSplatBlock), 0, st, P, V, B);
+        return;
+    }
     if (P.C == 5 && diff) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_multi<G, 5, true, false>), grid, dim3(kSplatBlock), 0, st, P, V, B);
     else if (P.C == 5) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_multi<G, 5, false, false>), grid, dim3(kSplatBlock), 0, st, P, V, B);
     else if (diff && row && whole && !P.record && !P.debug) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_multi<G, 4, true, true, false, false>), grid, dim3(kSplatBlock), 0, st, P, V, B);
@@ -4100,6 +4141,53 @@ static void gaussian_coeffs(float stddev, FilterCoeffs &f) {
     float w0 = std::fmaf(x4, q1, q0), w1 = q2;
     float x8 = x4 * x4;
     f.c[0] -= std::fmaf(x8, w1, w0);
+}
+
+/* Mitchell-Netravali's seven scalars a3 a2 a0 b3 b2 b1 b0 in f32, in mitchell.cpp:64-70's operation order */
+static void mitchell_coeffs(float b, float c, float *o) {
+    o[0] = (12.f - 9.f * b - 6.f * c);
+    o[1] = (-18.f + 12.f * b + 6.f * c);
+    o[2] = (6.f - 2.f * b);
+    o[3] = (-b - 6.f * c);
+    o[4] = (6.f * b + 30.f * c);
+    o[5] = (-12.f * b - 48.f * c);
+    o[6] = (8.f * b + 24.f * c);
+}
+/* The render's filter from the boundary's parameters: its kind, radius and host-computed scalars (dmath.h).
+ * literal: the filter is one whose row-splat instances hold its scalars as literals (the default Gaussian, tent of
+ * radius 1, Mitchell at B = C = 1/3, Catmull-Rom) -- verified bit for bit against what the host computes here */
+static bool filter_setup(const amvpt_params &Pp, FilterCoeffs &f, uint32_t &kind, bool *literal) {
+    if (Pp.rfilter > AMVPT_RFILTER_LANCZOS) return false;
+    kind = Pp.rfilter;
+    std::memset(&f, 0, sizeof(f));
+    bool lit = false;
+    switch (kind) {
+        case FILT_BOX: f.radius = .5f; break;
+        case FILT_GAUSSIAN: {
+            gaussian_coeffs(Pp.rfilter_stddev, f);
+            FilterCoeffs d;
+            gaussian_coeffs(0.5f, d);
+            lit = std::memcmp(&d, &f, sizeof(d)) == 0 && std::memcmp(&d.c[0], &kDefaultFilterHost[0], sizeof(d.c)) == 0;
+            break;
+        }
+        case FILT_TENT:
+            f.radius = Pp.rfilter_radius > 0.f ? Pp.rfilter_radius : 1.f;
+            f.c[0] = 1.f / f.radius;
+            lit = f.radius == 1.f && f.c[0] == 1.f;
+            break;
+        case FILT_MITCHELL:
+            f.radius = 2.f;
+            mitchell_coeffs(Pp.rfilter_b, Pp.rfilter_c, f.c);
+            lit = std::memcmp(&f.c[0], &kMitchellDefault[0], sizeof(kMitchellDefault)) == 0;
+            break;
+        case FILT_CATMULLROM: f.radius = 2.f; lit = true; break;
+        default: /* FILT_LANCZOS */
+            f.radius = Pp.rfilter_radius > 0.f ? Pp.rfilter_radius : 3.f;
+            f.c[0] = f.radius;
+            break;
+    }
+    if (literal) *literal = lit;
+    return true;
 }
 
 /* roctx range over a host scope (the reference's ScopedPhase, profiler.h:20-110): the render,
@@ -4345,6 +4433,7 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
     const uint32_t trav = opts.traversal;
     if (trav > 2) { set_error("amvpt_render: traversal must be 0 (auto), 1 (wave-uniform) or 2 (per-lane)"); return AMVPT_ERR_INVALID; }
     if (Pp.n_views == 0) { set_error("amvpt_render: n_views == 0"); return AMVPT_ERR_INVALID; }
+    if (Pp.rfilter > AMVPT_RFILTER_LANCZOS) { set_error("amvpt_render: unknown rfilter " + std::to_string(Pp.rfilter)); return AMVPT_ERR_INVALID; }
     if (Pp.multisensor && !Pp.batch && Pp.n_views != Pp.grid_x * Pp.grid_y) {
         set_error("amvpt_render: a grid MultiSensor needs n_views == grid_x * grid_y");
         return AMVPT_ERR_INVALID;
@@ -4499,16 +4588,19 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
         HIPCHK(hipStreamSynchronize(st));
     }
     P.valid_ray0 = (!Pp.hide_emitters && scene->dev.environment >= 0) ? 1u : 0u;
-    if (!P.box) gaussian_coeffs(Pp.rfilter_stddev, P.filt);
-    /* row-reduced splat (row_put): RGBW film, Gaussian filter, >= 16 samples per pixel and pass
-     * (a 16-lane row = one pixel); AMVPT_ROW_SPLAT=0 keeps the per-lane splat (A/B) */
+    /* row-reduced splat (row_put): RGBW film, >= 16 samples per pixel and pass (a 16-lane row = one pixel), and a
+     * filter whose scalars are literals in the row kernels (default_filter, filter_eval_lit; checked bit for bit by
+     * filter_setup): the default Gaussian in every render, tent of radius 1, Mitchell at B = C = 1/3 and Catmull-Rom
+     * in plain multi-view renders (whole-quilt film, no records, no debug: the instances launch_splat has for them).
+     * AMVPT_OPT_BLOCK_SPLAT (or AMVPT_ROW_SPLAT=0 of an A/B build) keeps the per-lane block window */
     {
-        /* ... and the default Gaussian (its coefficients are literals in the row kernels, default_filter) */
-        FilterCoeffs d;
-        gaussian_coeffs(0.5f, d);
-        const bool def_filt = !P.box && std::memcmp(&d, &P.filt, sizeof(d)) == 0 &&
-                              std::memcmp(&d.c[0], &kDefaultFilterHost[0], sizeof(d.c)) == 0;
-        P.row_splat = (K.row_splat && P.C == 4 && def_filt && P.pow2 && spp_pp >= 16) ? 1u : 0u;
+        bool literal = false;
+        filter_setup(Pp, P.filt, P.filt_kind, &literal);
+        const bool has_row = P.filt_kind == FILT_GAUSSIAN ||
+                             ((P.filt_kind == FILT_TENT || P.filt_kind == FILT_MITCHELL || P.filt_kind == FILT_CATMULLROM) &&
+                              G > 1 && whole_film && !records && !Pp.debug && !deterministic);
+        P.row_splat = (K.row_splat && !(opts.flags & AMVPT_OPT_BLOCK_SPLAT) && P.C == 4 && literal && has_row && P.pow2 &&
+                       spp_pp >= 16) ? 1u : 0u;
     }
     /* tiled slots: whole 4-row bands of a quilt row width divisible by 4, 16 samples per pixel and pass,
      * contiguous lane sets whose chunks start and end on band boundaries */
@@ -4947,7 +5039,10 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
             RoctxScope range_splat("amvpt splat (ImageBlock::put)");
             const dim3 sgrid((cn + kSplatBlock - 1) / kSplatBlock);
             T.begin(AMVPT_K_SPLAT, st);
-            if (G == 1 && P.C == 5) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_single<5>), sgrid, dim3(kSplatBlock), 0, st, P, B);
+            const bool any_filt = P.filt_kind > FILT_GAUSSIAN;   /* FK_ANY instances (tent, Mitchell, Catmull-Rom, Lanczos) */
+            if (G == 1 && P.C == 5 && any_filt) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_single<5, FK_ANY>), sgrid, dim3(kSplatBlock), 0, st, P, B);
+            else if (G == 1 && any_filt) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_single<4, FK_ANY>), sgrid, dim3(kSplatBlock), 0, st, P, B);
+            else if (G == 1 && P.C == 5) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_single<5>), sgrid, dim3(kSplatBlock), 0, st, P, B);
             else if (G == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_single<4>), sgrid, dim3(kSplatBlock), 0, st, P, B);
             else kSplat[dispatch_g(G)](sgrid, st, P, dviews, B, diff_rec);
             T.end(st);
@@ -5046,7 +5141,9 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
                 { const amvpt_status rs_ = run_suffix(cs, cn); if (rs_ != AMVPT_OK) return rs_; }
                 const dim3 sgrid((cn + kSplatBlock - 1) / kSplatBlock);
                 T.begin(AMVPT_K_SPLAT, st);
-                if (P.C == 5) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_adapt<5>), sgrid, dim3(kSplatBlock), 0, st, P, B);
+                if (P.C == 5 && P.filt_kind > FILT_GAUSSIAN) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_adapt<5, FK_ANY>), sgrid, dim3(kSplatBlock), 0, st, P, B);
+                else if (P.filt_kind > FILT_GAUSSIAN) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_adapt<4, FK_ANY>), sgrid, dim3(kSplatBlock), 0, st, P, B);
+                else if (P.C == 5) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_adapt<5>), sgrid, dim3(kSplatBlock), 0, st, P, B);
                 else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_adapt<4>), sgrid, dim3(kSplatBlock), 0, st, P, B);
                 T.end(st);
                 HIPCHK(hipGetLastError());
@@ -5146,6 +5243,20 @@ amvpt_status accumulate_impl(float *quilt, uint32_t qw, uint32_t qh, uint32_t C,
         hipLaunchKernelGGL(k_overflow_apply, dim3((uint32_t) ((n_ov + 255) / 256)), dim3(256), 0, st, quilt,
                            (uint64_t) qw * qh * C, (const uint4 *) ov, n_ov);
     HIPCHK(hipGetLastError());
+    return AMVPT_OK;
+}
+
+/* amvpt_rfilter_eval (host only): the render's filter_setup and the kernels' filter_eval */
+amvpt_status rfilter_eval_impl(const amvpt_params *params, const float *x, uint32_t n, float *out, float *radius) {
+    if (!params || (n && (!x || !out))) { set_error("amvpt_rfilter_eval: null argument"); return AMVPT_ERR_INVALID; }
+    FilterCoeffs f;
+    uint32_t kind = 0;
+    if (!filter_setup(*params, f, kind, nullptr)) {
+        set_error("amvpt_rfilter_eval: unknown rfilter " + std::to_string(params->rfilter));
+        return AMVPT_ERR_INVALID;
+    }
+    for (uint32_t i = 0; i < n; ++i) out[i] = filter_eval(kind, f, x[i]);
+    if (radius) *radius = f.radius;
     return AMVPT_OK;
 }
 

@@ -313,6 +313,82 @@ AD f2v_t gaussian_eval2(const FilterCoeffs &f, f2v_t x) {
     return f2v_t{vmax(v.x, 0.f), vmax(v.y, 0.f)};
 }
 
+/*
+ * The other reconstruction filters (src/rfilters/{tent,mitchell,catmullrom,lanczos}.cpp), DESIGN.md "Reconstruction
+ * filters".  Host and device evaluate the same functions (amvpt_rfilter_eval is the host side): f32, every operation
+ * rounded on its own, fused only where the reference writes dr::fmadd.  A filter's host-computed scalars travel in
+ * FilterCoeffs::c: tent c[0] = 1 / radius; Mitchell c[0..6] = a3 a2 a0 b3 b2 b1 b0; Lanczos c[0] = radius (lobes).
+ */
+#define HD __host__ __device__ __forceinline__
+enum : uint32_t { FILT_BOX = 0, FILT_GAUSSIAN = 1, FILT_TENT = 2, FILT_MITCHELL = 3, FILT_CATMULLROM = 4, FILT_LANCZOS = 5 };
+/* gaussian_eval for the host hook (the same operations) */
+HD float gaussian_eval_hd(const float *c, float x) {
+    float x2 = x * x;
+    float r0 = __builtin_fmaf(x2, c[1], c[0]), r1 = __builtin_fmaf(x2, c[3], c[2]), r2 = __builtin_fmaf(x2, c[5], c[4]),
+          r3 = __builtin_fmaf(x2, c[7], c[6]), r4 = __builtin_fmaf(x2, c[9], c[8]);
+    float x4 = x2 * x2;
+    float q0 = __builtin_fmaf(x4, r1, r0), q1 = __builtin_fmaf(x4, r3, r2);
+    float x8 = x4 * x4;
+    float w0 = __builtin_fmaf(x8, q1, q0);
+    float x16 = x8 * x8;
+    float v = __builtin_fmaf(x16, r4, w0);
+    return v > 0.f ? v : 0.f;
+}
+/* tent.cpp:53-55 */
+HD float tent_eval(float inv_radius, float x) {
+    const float v = 1.f - __builtin_fabsf(x * inv_radius);
+    return 0.f > v ? 0.f : v;   /* dr::maximum(0, v) */
+}
+/* mitchell.cpp:60-79 */
+HD float mitchell_eval(float a3, float a2, float a0, float b3, float b2, float b1, float b0, float x) {
+    x = __builtin_fabsf(x);
+    const float x2 = x * x, x3 = x2 * x;
+    const float in = __builtin_fmaf(a3, x3, __builtin_fmaf(a2, x2, a0));
+    const float out = __builtin_fmaf(b3, x3, __builtin_fmaf(b2, x2, __builtin_fmaf(b1, x, b0)));
+    const float result = (1.f / 6.f) * (x < 1.f ? in : out);
+    return x < 2.f ? result : 0.f;
+}
+/* catmullrom.cpp:39-54: plain products and sums, left to right, each rounded */
+HD float catmullrom_eval(float x) {
+    x = __builtin_fabsf(x);
+    const float x2 = x * x, x3 = x2 * x;
+    const float in = ((9.f * x3) + (-15.f * x2)) + 6.f;
+    const float out = (((-3.f * x3) + (15.f * x2)) + (-24.f * x)) + 12.f;
+    const float result = (1.f / 6.f) * (x < 1.f ? in : out);
+    return x < 2.f ? result : 0.f;
+}
+/* lanczos.cpp:57-67 (the sine is the platform's sinf: no bit-exactness claim for this filter) */
+HD float lanczos_eval(float radius, float x) {
+    x = __builtin_fabsf(x);
+    const float x1 = 3.14159265358979323846f * x, x2 = x1 / radius;
+    const float result = (sinf(x1) * sinf(x2)) / (x1 * x2);
+    return x < 5.9604644775390625e-08f ? 1.f : (x > radius ? 0.f : result);
+}
+/* any filter, by a (kernel-uniform) kind */
+HD float filter_eval(uint32_t kind, const FilterCoeffs &f, float x) {
+    const float *c = f.c;
+    switch (kind) {
+        case FILT_GAUSSIAN: return gaussian_eval_hd(c, x);
+        case FILT_TENT: return tent_eval(c[0], x);
+        case FILT_MITCHELL: return mitchell_eval(c[0], c[1], c[2], c[3], c[4], c[5], c[6], x);
+        case FILT_CATMULLROM: return catmullrom_eval(x);
+        case FILT_LANCZOS: return lanczos_eval(c[0], x);
+        default: return 1.f;   /* box */
+    }
+}
+/* the filters whose row-splat instances carry their scalars as compile-time literals (the reference's defaults):
+ * tent of radius 1, Mitchell at B = C = 1/3 -- the values mitchell_coeffs(1/3, 1/3) computes, which the host checks
+ * bit for bit before it picks these instances -- and Catmull-Rom, which has no parameters */
+constexpr float kMitchellDefault[7] = {0x1.cp+2f, -0x1.8p+3f, 0x1.555556p+2f, -0x1.2aaaaap+1f, 0x1.8p+3f, -0x1.4p+4f, 0x1.555556p+3f};
+template <uint32_t kKind> HD float filter_eval_lit(float x) {
+    static_assert(kKind == FILT_TENT || kKind == FILT_MITCHELL || kKind == FILT_CATMULLROM, "no literal form");
+    if constexpr (kKind == FILT_TENT) return tent_eval(1.f, x);
+    else if constexpr (kKind == FILT_MITCHELL)
+        return mitchell_eval(kMitchellDefault[0], kMitchellDefault[1], kMitchellDefault[2], kMitchellDefault[3],
+                             kMitchellDefault[4], kMitchellDefault[5], kMitchellDefault[6], x);
+    else return catmullrom_eval(x);
+}
+
 /* Warps (warp.h) */
 AD void disk_concentric(float u, float v, float &ox, float &oy) {
     float x = fmsub(2.f, u, 1.f), y = fmsub(2.f, v, 1.f);

@@ -35,6 +35,7 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
                          uint32_t record_pass);
 amvpt_status develop_impl(const float *film, float *out, uint32_t w, uint32_t h, uint32_t alpha, void *stream);
 amvpt_status release_impl(int device);
+amvpt_status rfilter_eval_impl(const amvpt_params *params, const float *x, uint32_t n, float *out, float *radius);
 amvpt_status accumulate_impl(float *quilt, uint32_t qw, uint32_t qh, uint32_t C, const float *win, uint32_t x0,
                              uint32_t y0, uint32_t w, uint32_t h, const uint32_t *ov, uint64_t n_ov, void *stream);
 extern uint64_t g_chunk_lanes;

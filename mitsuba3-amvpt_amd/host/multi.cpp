@@ -142,11 +142,19 @@ uint32_t group_size(const amvpt_params &p) {
 
 /* pixels around a rank's tiles its splats can reach (amvpt.dist.filter_border): ImageBlock::put's footprint
  * around a sample in the tile reaches ceil(radius - 1/2) cells (coalesced) or ceil(radius + 1/2) (not
- * coalesced), radius = 4 stddev for the Gaussian (gaussian.cpp:48-60); the box filter stays in its pixel.
+ * coalesced), radius = 4 stddev for the Gaussian (gaussian.cpp:48-60), the tent's `radius`, 2 for Mitchell and
+ * Catmull-Rom, the lobes for Lanczos; the box filter stays in its pixel.
  * At least 4, the default filter's border (radius 2) with a cell to spare. */
 static uint32_t filter_border(const amvpt_params &p) {
-    if (p.rfilter == AMVPT_RFILTER_BOX) return 4;
-    const float radius = 4.f * (p.rfilter_stddev > 0.f ? p.rfilter_stddev : .5f);
+    float radius;
+    switch (p.rfilter) {
+        case AMVPT_RFILTER_BOX: return 4;
+        case AMVPT_RFILTER_TENT: radius = p.rfilter_radius > 0.f ? p.rfilter_radius : 1.f; break;
+        case AMVPT_RFILTER_MITCHELL:
+        case AMVPT_RFILTER_CATMULLROM: radius = 2.f; break;
+        case AMVPT_RFILTER_LANCZOS: radius = p.rfilter_radius > 0.f ? p.rfilter_radius : 3.f; break;
+        default: radius = 4.f * (p.rfilter_stddev > 0.f ? p.rfilter_stddev : .5f); break;
+    }
     return std::max<uint32_t>(4, (uint32_t) std::ceil(radius + .5f));
 }
 

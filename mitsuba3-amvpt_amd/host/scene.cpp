@@ -91,6 +91,8 @@ struct FilmInfo {
     bool alpha = false;
     uint32_t rfilter = AMVPT_RFILTER_GAUSSIAN;
     float stddev = 0.5f;
+    float radius = 0.f;                       /* tent radius / Lanczos lobes (0: the filter has none) */
+    float b = 1.f / 3.f, c = 1.f / 3.f;       /* Mitchell-Netravali */
 };
 
 static FilmInfo make_film(const Properties &p) {
@@ -128,7 +130,22 @@ static FilmInfo make_film(const Properties &p) {
         std::string t = lower(rp.plugin);
         if (t == "gaussian") { f.rfilter = AMVPT_RFILTER_GAUSSIAN; f.stddev = (float) rp.get_float("stddev", 0.5); }
         else if (t == "box") f.rfilter = AMVPT_RFILTER_BOX;
-        else Throw("rfilter \"" + t + "\" is not implemented (gaussian, box)");
+        else if (t == "tent") {   /* tent.cpp:47-51 */
+            f.rfilter = AMVPT_RFILTER_TENT;
+            f.radius = (float) rp.get_float("radius", 1.0);
+            if (!(f.radius > 0.f)) Throw("tent: radius must be positive");
+        } else if (t == "mitchell") {   /* mitchell.cpp:50-58 */
+            f.rfilter = AMVPT_RFILTER_MITCHELL;
+            f.b = (float) rp.get_float("B", 1.0 / 3.0);
+            f.c = (float) rp.get_float("C", 1.0 / 3.0);
+        } else if (t == "catmullrom") f.rfilter = AMVPT_RFILTER_CATMULLROM;
+        else if (t == "lanczos") {   /* lanczos.cpp:52-55 */
+            f.rfilter = AMVPT_RFILTER_LANCZOS;
+            const long long lobes = rp.get_int("lobes", 3);
+            if (lobes < 1) Throw("lanczos: lobes must be at least 1");
+            f.radius = (float) lobes;
+        }
+        else Throw("rfilter \"" + t + "\" is not implemented (gaussian, box, tent, mitchell, catmullrom, lanczos)");
     }
     return f;
 }
@@ -798,6 +815,9 @@ static amvpt_params params_for(const amvpt_host_scene &S, const SensorInfo &sn, 
     p.film_alpha = sn.film.alpha;
     p.rfilter = sn.film.rfilter;
     p.rfilter_stddev = sn.film.stddev;
+    p.rfilter_radius = sn.film.radius;
+    p.rfilter_b = sn.film.b;
+    p.rfilter_c = sn.film.c;
     return p;
 }
 
