@@ -10,6 +10,9 @@
  *                                           spp, develop, evaluate)  integrator.cpp:30-42,
  *                                           dispatching to MVPathIntegrator::render mvpath.cpp:7-278
  *   amvpt_host_write_exr                 <- Film::write (hdrfilm.cpp, OpenEXR float32)
+ *   amvpt_host_display / _write_png      <- Program::display_image(screenshot) + Bitmap::write
+ *                                           (src/mitsuba/program.cpp:199-276)
+ *   amvpt_host_read_presets / _write_presets <- Preset::import_file / export_file (src/mitsuba/preset.h)
  *   amvpt_host_parse_fov / _perspective_projection
  *                                        <- parse_fov sensor.cpp:163-214,
  *                                           perspective_projection sensor.h:319-356
@@ -20,6 +23,7 @@
 #define AMVPT_HOST_H
 
 #include "amvpt.h"
+#include "amvpt_display.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -119,6 +123,51 @@ int amvpt_host_write_exr(const char *path, const float *data, uint32_t width, ui
                          uint32_t channels);
 int amvpt_host_read_exr(const char *path, float *data, uint32_t width, uint32_t height,
                         uint32_t channels);
+
+/*
+ * The display stage (amvpt_display.h; the reference's front end, src/mitsuba/program.cpp:199-276): render ->
+ * develop -> 8-bit sRGB quilt -> lenticular image of dst_w x dst_h, on the scene's cached device buffers and the
+ * current device, with one download at the end: out_host_u8 receives dst_h x dst_w x 3 bytes.  preset NULL:
+ * amvpt_host_preset_for_scene's.  quilt != 0 resamples the whole quilt instead; nearest != 0 picks texels instead
+ * of the bilinear blend.  The stage reads the cached film and never writes it.  _stream runs on a caller stream
+ * (hipStream_t; NULL: the default stream), as amvpt_host_render_stream does.
+ */
+int amvpt_host_display(amvpt_host_scene *scene, uint32_t sensor_index, uint32_t seed, uint32_t spp,
+                       const amvpt_display_preset *preset, int quilt, int nearest, uint32_t dst_w, uint32_t dst_h,
+                       uint8_t *out_host_u8, amvpt_counters *counters);
+int amvpt_host_display_stream(amvpt_host_scene *scene, uint32_t sensor_index, uint32_t seed, uint32_t spp,
+                              const amvpt_display_preset *preset, int quilt, int nearest, uint32_t dst_w,
+                              uint32_t dst_h, uint8_t *out_host_u8, void *stream, amvpt_counters *counters);
+
+/*
+ * The stage alone, without a render: sRGB quilt and display image of the developed frame that the last
+ * amvpt_host_render* (raw == 0) or amvpt_host_display* of this sensor left on the current device -- what the
+ * reference's front end does when a preset slider moves (program.cpp:200, m_update_view).  An error when no such
+ * frame is cached.  Renders are not bit-reproducible (float atomics), so this is also how one frame is shown twice.
+ */
+int amvpt_host_redisplay_stream(amvpt_host_scene *scene, uint32_t sensor_index, const amvpt_display_preset *preset,
+                                int quilt, int nearest, uint32_t dst_w, uint32_t dst_h, uint8_t *out_host_u8,
+                                void *stream);
+
+/* The default preset (LKG4x8) with `grid` set from the sensor's grid_x / grid_y; a batch sensor gives n x 1. */
+int amvpt_host_preset_for_scene(amvpt_host_scene *scene, uint32_t sensor_index, amvpt_display_preset *preset);
+
+/*
+ * The reference's presets.csv (preset.h:19-57), one preset per line:
+ *   name;center;focus;pitch;tilt;subp;view0;view1;grid0;grid1;flip_rgb
+ * Floats are written with nine significant digits, so that writing then reading gives the same values (the
+ * reference writes six and reads any number).  read fills at most `capacity` entries and sets *count to the
+ * number of presets in the file; names longer than 63 bytes are cut.
+ */
+typedef struct amvpt_host_named_preset {
+    char name[64];
+    amvpt_display_preset preset;
+} amvpt_host_named_preset;
+int amvpt_host_read_presets(const char *path, amvpt_host_named_preset *presets, uint32_t capacity, uint32_t *count);
+int amvpt_host_write_presets(const char *path, const amvpt_host_named_preset *presets, uint32_t count);
+
+/* PNG writer, 8-bit RGB (height x width x 3 bytes): stored deflate blocks, no compression library. */
+int amvpt_host_write_png(const char *path, const uint8_t *rgb, uint32_t width, uint32_t height);
 
 /* Known-answer hooks (sensor.cpp / sensor.h). fov_axis: "x","y","smaller","larger","diagonal". */
 double amvpt_host_parse_fov(double fov, const char *fov_axis, const char *focal_length, double aspect);

@@ -1,0 +1,213 @@
+"""
+amvpt.display -- the display stage: the developed quilt as 8-bit sRGB and the quilt interlaced into the
+native image of a lenticular light-field display (include/amvpt_display.h; the reference's front end,
+src/mitsuba/program.cpp:199-276 with the presets of src/mitsuba/preset.h).
+
+`srgb8`, `interlace` and `views` run the host entries over numpy arrays and need no device;
+`srgb8_device` / `interlace_device` launch the kernels over device pointers; `display` renders a scene and
+runs the whole stage on the device, downloading the display image once.
+"""
+import ctypes
+
+import numpy as np
+
+import amvpt
+from amvpt import Counters, f32, i32, u32
+
+ERR_INVALID = 1
+
+
+class Preset(ctypes.Structure):
+    """amvpt_display_preset: a lenticular display's calibration (Preset, preset.h:12-17)."""
+    _fields_ = [("center", f32), ("focus", f32), ("pitch", f32), ("tilt", f32), ("subp", f32),
+                ("view", f32 * 2), ("grid", i32 * 2), ("flip_rgb", u32)]
+
+    def __init__(self, center=-0.5, focus=-0.05, pitch=354.548, tilt=-0.114, subp=0.00013, view=(1.0, 1.0),
+                 grid=(4, 8), flip_rgb=False, name="LKG4x8"):
+        super().__init__(center, focus, pitch, tilt, subp, (f32 * 2)(*view), (i32 * 2)(*grid), 1 if flip_rgb else 0)
+        self.name = name
+
+    def values(self):
+        """The fields as a tuple of Python numbers (floats as the float32 values the library sees)."""
+        return (self.center, self.focus, self.pitch, self.tilt, self.subp, tuple(self.view), tuple(self.grid),
+                bool(self.flip_rgb))
+
+    def __eq__(self, other):
+        return isinstance(other, Preset) and self.values() == other.values() and self.name == other.name
+
+    def __repr__(self):
+        return "Preset(name=%r, center=%r, focus=%r, pitch=%r, tilt=%r, subp=%r, view=%r, grid=%r, flip_rgb=%r)" % (
+            (self.name,) + self.values())
+
+    @classmethod
+    def _from_c(cls, c, name="LKG4x8"):
+        return cls(c.center, c.focus, c.pitch, c.tilt, c.subp, tuple(c.view), tuple(c.grid), bool(c.flip_rgb), name)
+
+
+class _NamedPreset(ctypes.Structure):
+    _fields_ = [("name", ctypes.c_char * 64), ("preset", Preset)]
+
+
+_bound = False
+
+
+def _libs():
+    global _bound
+    L, H = amvpt.hip_lib(), amvpt.host_lib()
+    if not _bound:
+        vp, cp = ctypes.c_void_p, ctypes.c_int
+        pp = ctypes.POINTER(Preset)
+        L.amvpt_display_version.restype = u32
+        L.amvpt_display_default_preset.restype = Preset
+        L.amvpt_display_default_preset.argtypes = []
+        for fn, args in (("amvpt_srgb8", [vp, u32, u32, u32, vp, vp]),
+                         ("amvpt_srgb8_host", [vp, u32, u32, u32, vp]),
+                         ("amvpt_interlace", [vp, u32, u32, u32, pp, cp, cp, vp, u32, u32, vp]),
+                         ("amvpt_interlace_host", [vp, u32, u32, u32, pp, cp, cp, vp, u32, u32]),
+                         ("amvpt_interlace_views_host", [pp, vp, u32, u32])):
+            getattr(L, fn).restype = cp
+            getattr(L, fn).argtypes = args
+        H.amvpt_host_display.argtypes = [vp, u32, u32, u32, pp, cp, cp, u32, u32, vp, ctypes.POINTER(Counters)]
+        H.amvpt_host_display_stream.argtypes = [vp, u32, u32, u32, pp, cp, cp, u32, u32, vp, vp,
+                                                ctypes.POINTER(Counters)]
+        H.amvpt_host_redisplay_stream.argtypes = [vp, u32, pp, cp, cp, u32, u32, vp, vp]
+        H.amvpt_host_preset_for_scene.argtypes = [vp, u32, pp]
+        H.amvpt_host_read_presets.argtypes = [ctypes.c_char_p, vp, u32, ctypes.POINTER(u32)]
+        H.amvpt_host_write_presets.argtypes = [ctypes.c_char_p, vp, u32]
+        H.amvpt_host_write_png.argtypes = [ctypes.c_char_p, vp, u32, u32]
+        _bound = True
+    return L, H
+
+
+def _check_hip(rc, L):
+    if rc != 0:
+        raise RuntimeError(L.amvpt_last_error().decode())
+
+
+def version():
+    return _libs()[0].amvpt_display_version()
+
+
+def default_preset():
+    """The reference's LKG4x8 (amvpt_display_default_preset)."""
+    return Preset._from_c(_libs()[0].amvpt_display_default_preset())
+
+
+def srgb8(image):
+    """Developed float32 image (H, W, 3 or 4) -> (H, W, 3) uint8 sRGB; alpha is dropped (amvpt_srgb8_host)."""
+    L, _ = _libs()
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    if img.ndim != 3:
+        raise ValueError("srgb8: an (H, W, C) image is needed")
+    h, w, c = img.shape
+    out = np.empty((h, w, 3), dtype=np.uint8)
+    _check_hip(L.amvpt_srgb8_host(img.ctypes.data, c, w, h, out.ctypes.data), L)
+    return out
+
+
+def _src_u8(src):
+    s = np.ascontiguousarray(src)
+    if s.dtype != np.uint8 or s.ndim != 3:
+        raise ValueError("interlace: an (H, W, C) uint8 quilt is needed")
+    return s
+
+
+def interlace(src, preset=None, size=(1280, 720), quilt=False, nearest=False):
+    """8-bit quilt (H, W, 3 or 4) -> the (size[1], size[0], 3) uint8 lenticular image of `preset`
+    (amvpt_interlace_host); quilt=True resamples the whole quilt instead."""
+    L, _ = _libs()
+    s = _src_u8(src)
+    p = preset if preset is not None else default_preset()
+    w, h = int(size[0]), int(size[1])
+    out = np.empty((max(h, 0), max(w, 0), 3), dtype=np.uint8)
+    _check_hip(L.amvpt_interlace_host(s.ctypes.data, s.shape[1], s.shape[0], s.shape[2], ctypes.byref(p),
+                                      int(bool(quilt)), int(bool(nearest)), out.ctypes.data, w, h), L)
+    return out
+
+
+def views(preset=None, size=(1280, 720)):
+    """The view index every subpixel picks: (size[1], size[0], 3) int32 (amvpt_interlace_views_host)."""
+    L, _ = _libs()
+    p = preset if preset is not None else default_preset()
+    w, h = int(size[0]), int(size[1])
+    out = np.empty((max(h, 0), max(w, 0), 3), dtype=np.int32)
+    _check_hip(L.amvpt_interlace_views_host(ctypes.byref(p), out.ctypes.data, w, h), L)
+    return out
+
+
+def srgb8_device(image_ptr, channels, width, height, out_ptr, stream=None):
+    """amvpt_srgb8 over device pointers, ordered on `stream` (a hipStream_t handle; None: the default stream)."""
+    L, _ = _libs()
+    _check_hip(L.amvpt_srgb8(ctypes.c_void_p(image_ptr), channels, width, height, ctypes.c_void_p(out_ptr),
+                             ctypes.c_void_p(stream or 0)), L)
+
+
+def interlace_device(src_ptr, src_w, src_h, src_channels, dst_ptr, size, preset=None, quilt=False, nearest=False,
+                     stream=None):
+    """amvpt_interlace over device pointers: the src_h x src_w x src_channels uint8 quilt at src_ptr -> the
+    size[1] x size[0] x 3 uint8 image at dst_ptr, ordered on `stream`."""
+    L, _ = _libs()
+    p = preset if preset is not None else default_preset()
+    _check_hip(L.amvpt_interlace(ctypes.c_void_p(src_ptr), src_w, src_h, src_channels, ctypes.byref(p),
+                                 int(bool(quilt)), int(bool(nearest)), ctypes.c_void_p(dst_ptr), int(size[0]),
+                                 int(size[1]), ctypes.c_void_p(stream or 0)), L)
+
+
+def preset_for_scene(scene, sensor=0):
+    """The default preset with `grid` from the sensor's view grid (a batch sensor gives n x 1)."""
+    _, H = _libs()
+    p = Preset()
+    amvpt._check(H.amvpt_host_preset_for_scene(scene._h, sensor, ctypes.byref(p)), H)
+    return p
+
+
+def display(scene, preset=None, size=(1280, 720), quilt=False, nearest=False, sensor=0, seed=0, spp=0,
+            counters=None, stream=None, rerender=True):
+    """Render `scene` and run the display stage on the device (amvpt_host_display): render -> develop -> sRGB
+    quilt -> lenticular image, one download -> (size[1], size[0], 3) uint8.  preset None: preset_for_scene.
+    rerender=False runs the stage alone on the developed frame the last render / display of this sensor left on
+    the device (amvpt_host_redisplay_stream): another preset, size or mode for the same frame."""
+    _, H = _libs()
+    w, h = int(size[0]), int(size[1])
+    out = np.zeros((max(h, 0), max(w, 0), 3), dtype=np.uint8)
+    if not rerender:
+        amvpt._check(H.amvpt_host_redisplay_stream(scene._h, sensor,
+                                                   ctypes.byref(preset) if preset is not None else None,
+                                                   int(bool(quilt)), int(bool(nearest)), w, h,
+                                                   ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(stream or 0)), H)
+        return out
+    cnt = counters if counters is not None else Counters()
+    amvpt._check(H.amvpt_host_display_stream(scene._h, sensor, seed, spp,
+                                             ctypes.byref(preset) if preset is not None else None,
+                                             int(bool(quilt)), int(bool(nearest)), w, h,
+                                             ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(stream or 0),
+                                             ctypes.byref(cnt)), H)
+    return out
+
+
+def read_presets(path):
+    """The presets of a presets.csv (name;center;focus;pitch;tilt;subp;view0;view1;grid0;grid1;flip_rgb)."""
+    _, H = _libs()
+    n = u32()
+    amvpt._check(H.amvpt_host_read_presets(str(path).encode(), None, 0, ctypes.byref(n)), H)
+    buf = (_NamedPreset * max(1, n.value))()
+    amvpt._check(H.amvpt_host_read_presets(str(path).encode(), ctypes.addressof(buf), n.value, ctypes.byref(n)), H)
+    return [Preset._from_c(buf[i].preset, buf[i].name.decode()) for i in range(min(n.value, len(buf)))]
+
+
+def write_presets(path, presets):
+    _, H = _libs()
+    buf = (_NamedPreset * max(1, len(presets)))()
+    for i, p in enumerate(presets):
+        buf[i].name = p.name.encode()[:63]
+        ctypes.memmove(ctypes.addressof(buf[i].preset), ctypes.addressof(p), ctypes.sizeof(Preset))
+    amvpt._check(H.amvpt_host_write_presets(str(path).encode(), ctypes.addressof(buf), len(presets)), H)
+
+
+def write_png(path, image):
+    """(H, W, 3) uint8 -> an 8-bit RGB PNG (amvpt_host_write_png)."""
+    _, H = _libs()
+    img = np.ascontiguousarray(image)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError("write_png: an (H, W, 3) uint8 image is needed")
+    amvpt._check(H.amvpt_host_write_png(str(path).encode(), img.ctypes.data, img.shape[1], img.shape[0]), H)

@@ -429,6 +429,10 @@ struct amvpt_host_scene {
         amvpt_scene *scene = nullptr;
         float *film = nullptr, *image = nullptr;
         size_t film_bytes = 0, image_bytes = 0;
+        uint8_t *quilt8 = nullptr, *display8 = nullptr;   /* amvpt_host_display: the sRGB quilt, the display image */
+        uint32_t image_w = 0, image_h = 0, image_ch = 0;   /* the developed frame `image` holds (0: none), of image_sensor */
+        uint32_t image_sensor = 0;
+        size_t quilt8_bytes = 0, display8_bytes = 0;
     };
     std::mutex render_mu;                 /* one render of this scene at a time (its cached buffers) */
     std::vector<DeviceCache> devices;
@@ -444,6 +448,8 @@ struct amvpt_host_scene {
             if (d.scene) amvpt_scene_destroy(d.scene);
             if (d.film) (void) hipFree(d.film);
             if (d.image) (void) hipFree(d.image);
+            if (d.quilt8) (void) hipFree(d.quilt8);
+            if (d.display8) (void) hipFree(d.display8);
             (void) amvpt_release_device_memory(d.device);   /* the renders' lane arena on this device (ABI 10) */
             if (have) (void) hipSetDevice(cur);
         }
@@ -918,14 +924,112 @@ int amvpt_host_describe(amvpt_host_scene *s, uint32_t si, uint32_t seed, uint32_
 const char *amvpt_host_integrator_string(amvpt_host_scene *s) { return s ? s->integrator.text.c_str() : ""; }
 
 /* a device buffer of at least `bytes`, grown (never shrunk) across frames */
-static void ensure_buffer(float *&buf, size_t &have, size_t bytes, uint64_t &allocs) {
-    if (have >= bytes) return;
+static void *grown(void *buf, size_t &have, size_t bytes, uint64_t &allocs, const char *what) {
+    if (have >= bytes) return buf;
     if (buf) (void) hipFree(buf);
-    buf = nullptr;
     have = 0;
-    if (hipMalloc(&buf, bytes) != hipSuccess) throw std::runtime_error("hipMalloc of the film failed");
+    void *fresh = nullptr;
+    if (hipMalloc(&fresh, bytes) != hipSuccess) throw std::runtime_error(std::string("hipMalloc of the ") + what + " failed");
     have = bytes;
     ++allocs;
+    return fresh;
+}
+static void ensure_buffer(float *&buf, size_t &have, size_t bytes, uint64_t &allocs) {
+    float *old = buf;
+    buf = nullptr;   /* stays null if the allocation throws: `old` is freed by then */
+    buf = static_cast<float *>(grown(old, have, bytes, allocs, "film"));
+}
+static void ensure_buffer_u8(uint8_t *&buf, size_t &have, size_t bytes, uint64_t &allocs, const char *what) {
+    uint8_t *old = buf;
+    buf = nullptr;
+    buf = static_cast<uint8_t *>(grown(old, have, bytes, allocs, what));
+}
+
+/* One frame into the scene's cached ImageBlock on the current device, enqueued on `stream` (render_mu held):
+ * the device scene and the film are created on first use and kept. */
+static amvpt_host_scene::DeviceCache *render_cached(amvpt_host_scene *s, const mi::SensorInfo &sn, const amvpt_params &p,
+                                                    void *stream, amvpt_counters *counters) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+    amvpt_host_scene::DeviceCache *dc = nullptr;
+    for (auto &d : s->devices)
+        if (d.device == dev) dc = &d;
+    if (!dc) {
+        s->devices.emplace_back();
+        dc = &s->devices.back();
+        dc->device = dev;
+    }
+    if (!dc->scene) {
+        if (amvpt_scene_create(&s->desc, &dc->scene) != AMVPT_OK) throw std::runtime_error(amvpt_last_error());
+        ++s->scene_creates;
+    }
+    const hipStream_t st = (hipStream_t) stream;
+    const uint32_t C = amvpt_film_channels(&p);
+    const size_t npx = (size_t) p.film_width * p.film_height;
+    dc->image_w = dc->image_h = dc->image_ch = 0;   /* the film is rewritten: `image` no longer shows it */
+    ensure_buffer(dc->film, dc->film_bytes, npx * C * sizeof(float), s->buffer_allocs);
+    if (hipMemsetAsync(dc->film, 0, npx * C * sizeof(float), st) != hipSuccess)
+        throw std::runtime_error("hipMemsetAsync(film) failed");
+    /* the whole frame with explicit per-call options: no process-global knob takes part */
+    amvpt_lane_set lanes{};
+    lanes.lane_begin = 0;
+    lanes.lane_end = UINT64_MAX;
+    amvpt_film_window win{};
+    win.film = dc->film;
+    win.width = p.film_width;
+    win.height = p.film_height;
+    amvpt_render_opts opts{};
+    if (amvpt_render_ex(dc->scene, sn.views.data(), &p, &lanes, &win, stream, &opts, counters) != AMVPT_OK)
+        throw std::runtime_error(amvpt_last_error());
+    ++s->renders;
+    return dc;
+}
+
+/* the developed image of dc->film in dc->image, enqueued on `stream`; returns its size in bytes */
+static size_t develop_cached(amvpt_host_scene *s, amvpt_host_scene::DeviceCache *dc, const amvpt_params &p, void *stream) {
+    const size_t npx = (size_t) p.film_width * p.film_height;
+    const uint32_t T = p.film_alpha ? 4u : 3u;
+    const size_t bytes = npx * T * sizeof(float);
+    ensure_buffer(dc->image, dc->image_bytes, bytes, s->buffer_allocs);
+    if (amvpt_develop(dc->film, dc->image, p.film_width, p.film_height, p.film_alpha, stream) != AMVPT_OK)
+        throw std::runtime_error(amvpt_last_error());
+    dc->image_w = p.film_width, dc->image_h = p.film_height, dc->image_ch = T;
+    return bytes;
+}
+
+/* the developed frame in dc->image -> sRGB quilt -> display image -> out (host), all on `stream`; reads dc->image only */
+static void display_stage(amvpt_host_scene *s, amvpt_host_scene::DeviceCache *dc, const amvpt_display_preset *preset,
+                          int quilt, int nearest, uint32_t dst_w, uint32_t dst_h, uint8_t *out, void *stream) {
+    const hipStream_t st = (hipStream_t) stream;
+    const size_t qbytes = (size_t) dc->image_w * dc->image_h * 3, obytes = (size_t) dst_w * dst_h * 3;
+    ensure_buffer_u8(dc->quilt8, dc->quilt8_bytes, qbytes, s->buffer_allocs, "sRGB quilt");
+    ensure_buffer_u8(dc->display8, dc->display8_bytes, obytes, s->buffer_allocs, "display image");
+    if (amvpt_srgb8(dc->image, dc->image_ch, dc->image_w, dc->image_h, dc->quilt8, stream) != AMVPT_OK ||
+        amvpt_interlace(dc->quilt8, dc->image_w, dc->image_h, 3, preset, quilt, nearest, dc->display8, dst_w, dst_h,
+                        stream) != AMVPT_OK)
+        throw std::runtime_error(amvpt_last_error());
+    if (hipMemcpyAsync(out, dc->display8, obytes, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        throw std::runtime_error("copying the display image to the host failed");
+}
+
+/* the preset to use (NULL: the sensor's), checked with the size before any device work: the host entry's refusals */
+static amvpt_display_preset checked_preset(const amvpt_params &p, const amvpt_display_preset *preset, int quilt, int nearest,
+                                           uint32_t dst_w, uint32_t dst_h) {
+    amvpt_display_preset use;
+    if (preset) {
+        use = *preset;
+    } else {
+        use = amvpt_display_default_preset();
+        use.grid[0] = (int32_t) (p.grid_x ? p.grid_x : 1u);
+        use.grid[1] = (int32_t) (p.grid_y ? p.grid_y : 1u);
+    }
+    const uint8_t texel[3] = {0, 0, 0};
+    uint8_t sink[12];
+    if (amvpt_interlace_host(texel, 1, 1, 3, &use, quilt, nearest, sink, dst_w < 2 ? dst_w : 2, dst_h < 2 ? dst_h : 2) !=
+        AMVPT_OK)
+        throw std::runtime_error(amvpt_last_error());
+    return use;
 }
 
 int amvpt_host_render_stream(amvpt_host_scene *s, uint32_t si, uint32_t seed, uint32_t spp, int raw, float *out,
@@ -934,47 +1038,14 @@ int amvpt_host_render_stream(amvpt_host_scene *s, uint32_t si, uint32_t seed, ui
         if (!s || si >= s->sensors.size()) throw std::runtime_error("Scene::render(): sensor index out of bounds!");
         const mi::SensorInfo &sn = s->sensors[si];
         amvpt_params p = mi::params_for(*s, sn, seed, spp);
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) dev = 0;
         std::lock_guard<std::mutex> lock(s->render_mu);
-        amvpt_host_scene::DeviceCache *dc = nullptr;
-        for (auto &d : s->devices)
-            if (d.device == dev) dc = &d;
-        if (!dc) {
-            s->devices.emplace_back();
-            dc = &s->devices.back();
-            dc->device = dev;
-        }
-        if (!dc->scene) {
-            if (amvpt_scene_create(&s->desc, &dc->scene) != AMVPT_OK) throw std::runtime_error(amvpt_last_error());
-            ++s->scene_creates;
-        }
+        amvpt_host_scene::DeviceCache *dc = render_cached(s, sn, p, stream, counters);
         const hipStream_t st = (hipStream_t) stream;
-        const uint32_t C = amvpt_film_channels(&p);
-        const size_t npx = (size_t) p.film_width * p.film_height;
-        ensure_buffer(dc->film, dc->film_bytes, npx * C * sizeof(float), s->buffer_allocs);
-        if (hipMemsetAsync(dc->film, 0, npx * C * sizeof(float), st) != hipSuccess)
-            throw std::runtime_error("hipMemsetAsync(film) failed");
-        /* the whole frame with explicit per-call options: no process-global knob takes part */
-        amvpt_lane_set lanes{};
-        lanes.lane_begin = 0;
-        lanes.lane_end = UINT64_MAX;
-        amvpt_film_window win{};
-        win.film = dc->film;
-        win.width = p.film_width;
-        win.height = p.film_height;
-        amvpt_render_opts opts{};
-        if (amvpt_render_ex(dc->scene, sn.views.data(), &p, &lanes, &win, stream, &opts, counters) != AMVPT_OK)
-            throw std::runtime_error(amvpt_last_error());
-        ++s->renders;
         const float *src = dc->film;
-        size_t bytes = npx * C * sizeof(float);
+        size_t bytes = (size_t) p.film_width * p.film_height * amvpt_film_channels(&p) * sizeof(float);
         if (!raw) {
-            const uint32_t T = p.film_alpha ? 4u : 3u;
-            bytes = npx * T * sizeof(float);
-            ensure_buffer(dc->image, dc->image_bytes, bytes, s->buffer_allocs);
-            if (amvpt_develop(dc->film, dc->image, p.film_width, p.film_height, p.film_alpha, stream) != AMVPT_OK)
-                throw std::runtime_error(amvpt_last_error());
+            bytes = develop_cached(s, dc, p, stream);
+            dc->image_sensor = si;
             src = dc->image;
         }
         if (hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, st) != hipSuccess ||
@@ -982,6 +1053,65 @@ int amvpt_host_render_stream(amvpt_host_scene *s, uint32_t si, uint32_t seed, ui
             throw std::runtime_error("copying the image to the host failed");
         return 0;
     });
+}
+
+/* the default preset with the sensor's view grid (a batch sensor's n views lie side by side: n x 1) */
+int amvpt_host_preset_for_scene(amvpt_host_scene *s, uint32_t si, amvpt_display_preset *preset) {
+    return guarded([&] {
+        if (!s || si >= s->sensors.size()) throw std::runtime_error("Scene::render(): sensor index out of bounds!");
+        if (!preset) throw std::runtime_error("amvpt_host_preset_for_scene: null preset");
+        const amvpt_params p = mi::params_for(*s, s->sensors[si], 0, 0);
+        *preset = amvpt_display_default_preset();
+        preset->grid[0] = (int32_t) (p.grid_x ? p.grid_x : 1u);
+        preset->grid[1] = (int32_t) (p.grid_y ? p.grid_y : 1u);
+        return 0;
+    });
+}
+
+/* render -> develop -> k_srgb8 -> k_interlace on the cached device buffers and `stream`; one download at the end */
+int amvpt_host_display_stream(amvpt_host_scene *s, uint32_t si, uint32_t seed, uint32_t spp,
+                              const amvpt_display_preset *preset, int quilt, int nearest, uint32_t dst_w, uint32_t dst_h,
+                              uint8_t *out, void *stream, amvpt_counters *counters) {
+    return guarded([&] {
+        if (!s || si >= s->sensors.size()) throw std::runtime_error("Scene::render(): sensor index out of bounds!");
+        if (!out) throw std::runtime_error("amvpt_host_display: null out_host_u8");
+        const mi::SensorInfo &sn = s->sensors[si];
+        amvpt_params p = mi::params_for(*s, sn, seed, spp);
+        const amvpt_display_preset use = checked_preset(p, preset, quilt, nearest, dst_w, dst_h);
+        std::lock_guard<std::mutex> lock(s->render_mu);
+        amvpt_host_scene::DeviceCache *dc = render_cached(s, sn, p, stream, counters);
+        (void) develop_cached(s, dc, p, stream);
+        dc->image_sensor = si;
+        display_stage(s, dc, &use, quilt, nearest, dst_w, dst_h, out, stream);
+        return 0;
+    });
+}
+
+/* the stage alone, on the developed frame the last render or display of this sensor left on the current device */
+int amvpt_host_redisplay_stream(amvpt_host_scene *s, uint32_t si, const amvpt_display_preset *preset, int quilt, int nearest,
+                                uint32_t dst_w, uint32_t dst_h, uint8_t *out, void *stream) {
+    return guarded([&] {
+        if (!s || si >= s->sensors.size()) throw std::runtime_error("Scene::render(): sensor index out of bounds!");
+        if (!out) throw std::runtime_error("amvpt_host_redisplay: null out_host_u8");
+        const amvpt_params p = mi::params_for(*s, s->sensors[si], 0, 0);
+        const amvpt_display_preset use = checked_preset(p, preset, quilt, nearest, dst_w, dst_h);
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess) throw std::runtime_error("amvpt_host_redisplay: no HIP device visible");
+        std::lock_guard<std::mutex> lock(s->render_mu);
+        amvpt_host_scene::DeviceCache *dc = nullptr;
+        for (auto &d : s->devices)
+            if (d.device == dev) dc = &d;
+        if (!dc || !dc->image_w || dc->image_sensor != si)
+            throw std::runtime_error("amvpt_host_redisplay: no developed frame of this sensor is cached on the current device "
+                                     "(render or display it first)");
+        display_stage(s, dc, &use, quilt, nearest, dst_w, dst_h, out, stream);
+        return 0;
+    });
+}
+
+int amvpt_host_display(amvpt_host_scene *s, uint32_t si, uint32_t seed, uint32_t spp, const amvpt_display_preset *preset,
+                       int quilt, int nearest, uint32_t dst_w, uint32_t dst_h, uint8_t *out, amvpt_counters *counters) {
+    return amvpt_host_display_stream(s, si, seed, spp, preset, quilt, nearest, dst_w, dst_h, out, nullptr, counters);
 }
 
 int amvpt_host_render(amvpt_host_scene *s, uint32_t si, uint32_t seed, uint32_t spp, int raw, float *out,

@@ -1,0 +1,64 @@
+#!/usr/bin/env python3
+"""Renders a scene to the 8-bit quilt PNG and the interlaced PNG of a lenticular display.
+
+    python tools/quilt_display.py [scene.xml] [-D key=value ...] [--preset NAME --presets presets.csv]
+                                  [--size W H] [--nearest] [--out-dir DIR]
+
+Without arguments: scenes/cbox_grid.xml at a small resolution, the default preset (LKG4x8) with the scene's view
+grid, a 1280 x 720 display, written to out/<scene>_quilt.png and out/<scene>_display.png.  The frame is rendered once;
+both images come from that frame.
+"""
+import argparse
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(REPO, "mitsuba3-amvpt_amd"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("scene", nargs="?", default=os.path.join(REPO, "scenes", "cbox_grid.xml"))
+    ap.add_argument("-D", dest="defines", action="append", default=[], metavar="key=value")
+    ap.add_argument("--presets", help="a presets.csv to take --preset from")
+    ap.add_argument("--preset", help="name of a preset in --presets (default: LKG4x8 with the scene's grid)")
+    ap.add_argument("--size", type=int, nargs=2, default=(1280, 720), metavar=("W", "H"))
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--spp", type=int, default=0)
+    ap.add_argument("--nearest", action="store_true")
+    ap.add_argument("--out-dir", default=os.path.join(REPO, "out"))
+    a = ap.parse_args()
+
+    import amvpt
+    import amvpt.display as D
+
+    defines = dict(d.split("=", 1) for d in a.defines)
+    if os.path.basename(a.scene) == "cbox_grid.xml" and not a.defines:
+        defines = dict(res=128, gx=4, gy=2, spp=16)
+    scene = amvpt.load_file(a.scene, **defines)
+    preset = None
+    if a.preset:
+        if not a.presets:
+            ap.error("--preset needs --presets")
+        found = [p for p in D.read_presets(a.presets) if p.name == a.preset]
+        if not found:
+            ap.error("no preset %r in %s" % (a.preset, a.presets))
+        preset = found[-1]
+    w, h, _, _ = scene.film_info()
+    cnt = amvpt.Counters()
+    # one render; the 8-bit quilt from its download (the host entry gives the device's bytes), the display image
+    # from the stage run on the frame the render left on the device
+    quilt = D.srgb8(amvpt.render(scene, seed=a.seed, spp=a.spp, counters=cnt))
+    image = D.display(scene, preset, size=tuple(a.size), nearest=a.nearest, rerender=False)
+    os.makedirs(a.out_dir, exist_ok=True)
+    stem = os.path.join(a.out_dir, os.path.splitext(os.path.basename(a.scene))[0])
+    D.write_png(stem + "_quilt.png", quilt)
+    D.write_png(stem + "_display.png", image)
+    used = preset if preset is not None else D.preset_for_scene(scene)
+    print("%s: quilt %d x %d -> %s_quilt.png, display %d x %d (%s, grid %d x %d) -> %s_display.png, %d lanes" % (
+        os.path.basename(a.scene), w, h, stem, a.size[0], a.size[1], used.name, used.grid[0], used.grid[1], stem,
+        cnt.lanes))
+
+
+if __name__ == "__main__":
+    main()
