@@ -101,28 +101,6 @@ struct BNode { Box box; uint32_t left_or_first, count, axis = 0; };
 #endif
 static uint32_t g_bvh_max_leaf = 4;
 static float g_bvh_trav_cost = 0.f;
-/* depth of the LDS treelets (dscene.h DScene::tnodes), 0: none (A/B builds: EXTRA=-DAMVPT_TREELET_DEPTH=n);
- * 2^depth - 1 nodes at most, 32 B each */
-#ifndef AMVPT_TREELETS
-#define AMVPT_TREELETS 0   /* the walks that stage treelets (amvpt_render.hip); 0: none, so none are built */
-#endif
-#ifndef AMVPT_TREELET_DEPTH
-#define AMVPT_TREELET_DEPTH ((AMVPT_TREELETS & 5) ? 8 : 0)   /* any-hit walks (k_shadow, k_vis): 255 nodes, 8 KB */
-#endif
-#ifndef AMVPT_OCT_TREELET_DEPTH
-#define AMVPT_OCT_TREELET_DEPTH ((AMVPT_TREELETS & 2) ? 6 : 0)   /* closest hit: 8 octant treelets, 8 x 63 nodes, 16 KB */
-#endif
-/* direction-octant node orderings for the per-lane closest-hit walks of large BVHs (A/B builds:
- * EXTRA=-DAMVPT_OCT_BVH=0 keeps one copy); a build-time choice, never a process-global knob */
-/* the two-box BVH (dscene.h DNode2) for the per-lane suffix walks of large BVHs (A/B builds: EXTRA=-DAMVPT_BVH2=0
- * keeps the threaded walks) */
-#ifndef AMVPT_BVH2
-#define AMVPT_BVH2 1
-#endif
-#ifndef AMVPT_OCT_BVH
-#define AMVPT_OCT_BVH 1
-#endif
-static const uint32_t g_treelet_depth = AMVPT_TREELET_DEPTH, g_oct_treelet_depth = AMVPT_OCT_TREELET_DEPTH;
 
 struct Builder {
     std::vector<BuildPrim> &prims;
@@ -210,19 +188,17 @@ struct Builder {
      * axis first for a positive direction, the upper one first for a negative direction.  The
      * skip links are local to the copy, so octant copy o is the array at o * n_nodes.
      */
-    void flatten(uint32_t ni, std::vector<DNode> &out, uint32_t oct = 0, uint32_t base = 0,
-                 std::vector<uint32_t> *pos = nullptr) const {
+    void flatten(uint32_t ni, std::vector<DNode> &out, uint32_t oct = 0, uint32_t base = 0) const {
         const BNode &bn = nodes[ni];
         const uint32_t at = (uint32_t) out.size();
-        if (pos) (*pos)[ni] = at;
         DNode d{};
         for (int i = 0; i < 3; ++i) { d.lo[i] = bn.box.lo[i]; d.hi[i] = bn.box.hi[i]; }
         d.first = bn.count ? bn.left_or_first : 0u;
         out.push_back(d);
         if (!bn.count) {
             const uint32_t near = (oct >> bn.axis) & 1u;
-            flatten(bn.left_or_first + near, out, oct, base, pos);
-            flatten(bn.left_or_first + (near ^ 1u), out, oct, base, pos);
+            flatten(bn.left_or_first + near, out, oct, base);
+            flatten(bn.left_or_first + (near ^ 1u), out, oct, base);
         }
         out[at].skip_count = (((uint32_t) out.size() - base) & kNodeSkipMask) | (bn.count << kNodeCountShift);
     }
@@ -245,26 +221,6 @@ struct Builder {
         out[at].ref[0] = refs[0];
         out[at].ref[1] = refs[1];
         return at;
-    }
-    /* the treelet of one ordering: the nodes of depth < depth_cut in the same depth-first order, skip links
-     * local to the treelet; an inner node at depth depth_cut - 1 is a portal to its subtree in the global
-     * copy (gpos: each builder node's index in that copy's array, including the copy's base) */
-    void flatten_top(uint32_t ni, std::vector<DNode> &out, uint32_t oct, uint32_t depth, uint32_t depth_cut,
-                     const std::vector<uint32_t> &gpos, uint32_t gbase, uint32_t base) const {
-        const BNode &bn = nodes[ni];
-        const uint32_t at = (uint32_t) out.size();
-        DNode d{};
-        for (int i = 0; i < 3; ++i) { d.lo[i] = bn.box.lo[i]; d.hi[i] = bn.box.hi[i]; }
-        d.first = bn.count ? bn.left_or_first : 0u;
-        const bool portal = !bn.count && depth + 1 >= depth_cut;
-        if (portal) d.first = kPortal | (gpos[ni] - gbase);   /* index local to the copy, as its skip links */
-        out.push_back(d);
-        if (!bn.count && !portal) {
-            const uint32_t near = (oct >> bn.axis) & 1u;
-            flatten_top(bn.left_or_first + near, out, oct, depth + 1, depth_cut, gpos, gbase, base);
-            flatten_top(bn.left_or_first + (near ^ 1u), out, oct, depth + 1, depth_cut, gpos, gbase, base);
-        }
-        out[at].skip_count = (((uint32_t) out.size() - base) & kNodeSkipMask) | (bn.count << kNodeCountShift);
     }
 };
 
@@ -493,16 +449,8 @@ static void scene_bsphere(const amvpt_scene_desc *d, float center[3], float &rad
     radius = std::max(ray_eps, radius * (1.f + ray_eps));
 }
 
-#ifndef AMVPT_BVH_OUTER
-#define AMVPT_BVH_OUTER 2    /* up to kOuterMax rectangles stay out of the BVH: 2 in every scene (the brute-force
-                                     * scenes' coherent walks too: config-M k_vis 44.2 -> 35.3 ms, r05u), 1 in scenes of
-                                     * more than kBrutePrims primitives only, 0 none (A/B) */
-#endif
 static constexpr uint32_t kBrutePrimsHost = 48;   /* dgeom.h kBrutePrims: brute-force scenes have no BVH walk */
 static constexpr float kInf32 = std::numeric_limits<float>::infinity();
-#ifndef AMVPT_BOX_SCREEN
-#define AMVPT_BOX_SCREEN 1   /* box meshes of brute-force scenes get DBox records (0: none, A/B) */
-#endif
 /*
  * Box meshes (dscene.h DBox): a mesh shape of 12 triangles whose vertices map, through the shape's
  * to_object (in double), to corners of [-1, 1]^3 within 1e-5, every triangle lying in one face plane, two
@@ -730,9 +678,10 @@ amvpt_status amvpt_scene_create(const amvpt_scene_desc *d, amvpt_scene **out) {
         for (int k = 0; k < 3; ++k) { scene_lo[k] = std::min(scene_lo[k], bp.box.lo[k]); scene_hi[k] = std::max(scene_hi[k], bp.box.hi[k]); }
     /* BVH scenes with a few rectangles (a room's walls and lights): the rectangles stay out of the BVH and
      * every walk tests them first (DScene::outer, dgeom.h outer_closest / outer_any) -- their boxes span the
-     * scene, so every ray crossing it descended to their leaves and tested them in divergent leaf code */
+     * scene, so every ray crossing it descended to their leaves and tested them in divergent leaf code.  In every
+     * scene, the brute-force scenes' coherent walks too: config-M k_vis 44.2 -> 35.3 ms (r05u) */
     std::vector<uint32_t> outer_idx;
-    if (AMVPT_BVH_OUTER && (scene_prims.size() > kBrutePrimsHost || AMVPT_BVH_OUTER >= 2)) {
+    {
         std::vector<BuildPrim> keep;
         for (const BuildPrim &bp : bprims) {
             if (scene_prims[bp.idx].type == PRIM_RECT) outer_idx.push_back(bp.idx);
@@ -741,15 +690,13 @@ amvpt_status amvpt_scene_create(const amvpt_scene_desc *d, amvpt_scene **out) {
         if (outer_idx.size() <= kOuterMax && !keep.empty()) bprims.swap(keep);
         else outer_idx.clear();
     }
-    std::vector<DNode> nodes, tnodes, onodes;
+    std::vector<DNode> nodes;
     std::vector<DNode2> nodes2;   /* the two-box BVH (empty: none) */
     std::vector<DNode2h> nodes2h; /* its float16 form */
     float n2_center[3] = {0.f, 0.f, 0.f}, n2_scale = 1.f;
     uint32_t bvh2_depth = 0;
     std::vector<DPrim> prims;
     uint32_t oct_stride = 0;   /* nodes per octant copy (0: one copy) */
-    uint32_t t_stride = 0;     /* nodes of the first ordering's treelet (0: none) */
-    uint32_t o_stride = 0;     /* nodes per octant treelet (0: none) */
     if (bprims.empty()) {
         /* one inner node with an empty box: every ray misses it and skips to the end */
         DNode root{};
@@ -763,11 +710,7 @@ amvpt_status amvpt_scene_create(const amvpt_scene_desc *d, amvpt_scene **out) {
         b.nodes.resize(1);
         b.build(0, 0, (uint32_t) bprims.size(), 0);
         nodes.reserve(b.nodes.size());
-        /* per-ordering positions of the build nodes: only the treelet builds read them */
-        const bool want_pos = g_treelet_depth > 0 || g_oct_treelet_depth > 0;
-        std::vector<std::vector<uint32_t>> gpos(want_pos ? 8 : 1);
-        if (want_pos) for (auto &g : gpos) g.assign(b.nodes.size(), 0u);
-        b.flatten(0, nodes, 0, 0, want_pos ? &gpos[0] : nullptr);
+        b.flatten(0, nodes);
         if (nodes.size() > kNodeSkipMask) {
             set_error("BVH too large (more than 2^28 nodes)");
             return AMVPT_ERR_INVALID;
@@ -777,27 +720,14 @@ amvpt_status amvpt_scene_create(const amvpt_scene_desc *d, amvpt_scene **out) {
          * box-test range early */
         const uint32_t n0 = (uint32_t) nodes.size();
         const uint64_t lds_b = (uint64_t) n0 * sizeof(DNode) + bprims.size() * sizeof(DPrim);
-        if (AMVPT_OCT_BVH && n0 > kUniformNodeLimit && lds_b > kLdsSceneBytes && (uint64_t) n0 * 8 <= kNodeSkipMask) {
+        if (n0 > kUniformNodeLimit && lds_b > kLdsSceneBytes && (uint64_t) n0 * 8 <= kNodeSkipMask) {
             nodes.reserve((size_t) n0 * 8);
-            for (uint32_t o = 1; o < 8; ++o) b.flatten(0, nodes, o, o * n0, want_pos ? &gpos[o] : nullptr);
+            for (uint32_t o = 1; o < 8; ++o) b.flatten(0, nodes, o, o * n0);
             oct_stride = n0;
-        }
-        /* LDS treelets for BVHs the walks read from global memory (neither wave-uniform-small nor staged
-         * whole): one per node ordering */
-        if (g_treelet_depth > 0 && n0 > kUniformNodeLimit && lds_b > kLdsSceneBytes) {
-            b.flatten_top(0, tnodes, 0, 0, g_treelet_depth, gpos[0], 0, 0);
-            t_stride = (uint32_t) tnodes.size();
-        }
-        if (g_oct_treelet_depth > 0 && oct_stride) {
-            for (uint32_t o = 0; o < 8; ++o) {
-                const uint32_t base = (uint32_t) onodes.size();
-                b.flatten_top(0, onodes, o, 0, g_oct_treelet_depth, gpos[o], o * n0, base);
-                if (o == 0) o_stride = (uint32_t) onodes.size();
-            }
         }
         /* the two-box BVH of the per-lane suffix walks (BVHs read from device memory, leaves addressable in a
          * reference, at most kStack2 inner nodes deep) */
-        if (AMVPT_BVH2 && n0 > kUniformNodeLimit && lds_b > kLdsSceneBytes && bprims.size() <= kRef2FirstMask) {
+        if (n0 > kUniformNodeLimit && lds_b > kLdsSceneBytes && bprims.size() <= kRef2FirstMask) {
             uint32_t depth = 0;
             if (b.nodes[0].count) {
                 /* a root leaf: one node with the leaf and an empty second child */
@@ -923,18 +853,16 @@ amvpt_status amvpt_scene_create(const amvpt_scene_desc *d, amvpt_scene **out) {
     /* box meshes of brute-force scenes (dscene.h DBox; dgeom.h box_walk) */
     std::vector<DBox> boxes;
     std::vector<DPrim> box_prims, loose_prims;
-    if (AMVPT_BOX_SCREEN && prims.size() <= 48) find_boxes(d, prims, boxes, box_prims, loose_prims);
+    if (prims.size() <= kBrutePrimsHost) find_boxes(d, prims, boxes, box_prims, loose_prims);
     const uint32_t n_boxes = (uint32_t) boxes.size(), n_loose = (uint32_t) loose_prims.size();
     if (boxes.empty()) boxes.resize(1);
     if (box_prims.empty()) box_prims.resize(1);
     if (loose_prims.empty()) loose_prims.resize(1);
-    void *p_nodes, *p_prims, *p_shapes, *p_bsdfs, *p_emit, *p_vpos, *p_vnrm, *p_vuv, *p_faces, *p_farea, *p_tnodes, *p_onodes, *p_sph;
+    void *p_nodes, *p_prims, *p_shapes, *p_bsdfs, *p_emit, *p_vpos, *p_vnrm, *p_vuv, *p_faces, *p_farea, *p_sph;
     void *p_boxes, *p_box_prims, *p_loose, *p_outer, *p_nodes2, *p_nodes2h;
-    if (tnodes.empty()) tnodes.resize(1);   /* keep a valid pointer */
     const uint32_t n_nodes2 = (uint32_t) nodes2.size();
     if (nodes2.empty()) nodes2.resize(1);
     if (nodes2h.empty()) nodes2h.resize(1);
-    if (onodes.empty()) onodes.resize(1);
     amvpt_status st;
 #define UP(vec, ptr)                                                                      \
     if ((st = upload(vec.data(), vec.size() * sizeof(vec[0]), &ptr)) != AMVPT_OK) {       \
@@ -942,7 +870,7 @@ amvpt_status amvpt_scene_create(const amvpt_scene_desc *d, amvpt_scene **out) {
         return st;                                                                        \
     }
     UP(nodes, p_nodes) UP(prims, p_prims) UP(shapes, p_shapes) UP(bsdfs, p_bsdfs) UP(emitters, p_emit)
-    UP(vpos, p_vpos) UP(vnrm, p_vnrm) UP(vuv, p_vuv) UP(faces, p_faces) UP(face_area, p_farea) UP(tnodes, p_tnodes) UP(onodes, p_onodes)
+    UP(vpos, p_vpos) UP(vnrm, p_vnrm) UP(vuv, p_vuv) UP(faces, p_faces) UP(face_area, p_farea)
     UP(sph_prims, p_sph) UP(boxes, p_boxes) UP(box_prims, p_box_prims) UP(loose_prims, p_loose) UP(outer, p_outer)
     UP(nodes2, p_nodes2) UP(nodes2h, p_nodes2h)
 #undef UP
@@ -959,10 +887,6 @@ amvpt_status amvpt_scene_create(const amvpt_scene_desc *d, amvpt_scene **out) {
     D.face_area = (const float *) p_farea;
     D.n_nodes = oct_stride ? oct_stride : (uint32_t) nodes.size();
     D.oct_stride = oct_stride;
-    D.tnodes = (const DNode *) p_tnodes;
-    D.t_stride = t_stride;
-    D.onodes = (const DNode *) p_onodes;
-    D.o_stride = o_stride;
     D.sph_prims = (const uint32_t *) p_sph;
     D.n_sph = n_sph;
     sc->n_sph = n_sph;

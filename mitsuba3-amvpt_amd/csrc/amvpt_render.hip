@@ -26,7 +26,6 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <memory>
@@ -41,6 +40,112 @@
 #define AMVPT_TU_LOCAL static
 #else
 #define AMVPT_TU_LOCAL
+#endif
+
+/*
+ * Tuning constants.  Each keeps an #ifndef so that a variant library can be built with make EXTRA=-DAMVPT_X=n
+ * (Makefile BUILD / LIB / EXTRA) and measured against the default; the note at each one records the measurement
+ * that set it.  Nothing here selects between code paths: run-time path selection is amvpt_render_opts.flags.
+ * The one exception is AMVPT_VIS_RAYS, which is fixed at 2 (see its note).
+ */
+#ifndef AMVPT_WIN_H
+#define AMVPT_WIN_H 8   /* rows of the block-wide splat window (kWinH) */
+#endif
+#ifndef AMVPT_SPLAT_BLOCK
+#define AMVPT_SPLAT_BLOCK 256   /* threads per splat block (kSplatBlock, see slot_lane) */
+#endif
+/* Row stride of the window: rows of ww cells are laid out rs cells apart with rs % 32 == 16,
+ * so consecutive rows start 32 banks apart for the 64-bit cells (2 * rs mod 64 = 32): lanes
+ * whose reprojected footprints straddle a row boundary stop colliding on banks
+ * (measured: splat 206 -> 187 ms at config M; rs = ww, or % 32 in {1, 8, 17, 24}: 200-207 ms).
+ * The 112-cell width leaves room for the padding (5 blocks per CU either way). */
+#ifndef AMVPT_WIN_RS
+#define AMVPT_WIN_RS 16
+#endif
+#ifndef AMVPT_WIN_W
+#define AMVPT_WIN_W 112
+#endif
+#ifndef AMVPT_WAVE_WIN_W
+#define AMVPT_WAVE_WIN_W 32   /* cells per row of a wave's own splat window (kWaveWinW) */
+#endif
+#ifndef AMVPT_BIN_CELL_BITS
+#define AMVPT_BIN_CELL_BITS 2   /* origin cells per axis of the bin key: 2^bits; 3 (4096 keys): walks 3 ms faster, sort 16 ms slower (r05d) */
+#endif
+#ifndef AMVPT_BIN_UNROLL
+#define AMVPT_BIN_UNROLL 4   /* entries per thread in flight in k_bin_sort's passes (one 1024-thread block per partition) */
+#endif
+/* waves per SIMD the suffix walks' register allocation must allow (latency-bound dependent node loads):
+ * k_extend at 6 (80 VGPRs) took the mesh frame 599 -> 609 Msamples/s; 8 (64 VGPRs, 48 B of spills)
+ * 606; k_shadow keeps its own allocation (r03k) */
+#ifndef AMVPT_EXTEND_WAVES
+#define AMVPT_EXTEND_WAVES 6
+#endif
+#ifndef AMVPT_SHADOW_WAVES
+#define AMVPT_SHADOW_WAVES 1   /* k_shadow's launch bound: no register cap (see AMVPT_EXTEND_WAVES) */
+#endif
+/* waves per SIMD k_bounce's register allocation must allow: 5 (<= 96 VGPRs, from 101 at 4) hides
+ * more of the state loads and the fused NEE walk (109.7 vs 118.3 ms per config-M frame, A/B r02z) */
+#ifndef AMVPT_BOUNCE_WAVES
+#define AMVPT_BOUNCE_WAVES 5
+#endif
+#ifndef AMVPT_FUSED_BLOCKS
+/* blocks per queue partition (x kQParts blocks of 256 threads), more than are resident at once:
+ * blocks that start late find their partition partly drained, which evens out the tail
+ * (config M, 2^23-lane chunks, suffix ms: 5 -> 163.7, 8 -> 149.0, 16 -> 144.8, 24..64 -> 144.8,
+ * r02fb; 2^25-lane chunks: 12 -> 135.2, 16 -> 133.5, 24 -> 132.4, 32 -> 132.7, r02fm) */
+#define AMVPT_FUSED_BLOCKS 24
+#endif
+#ifndef AMVPT_FUSED_WAVES
+/* 6 waves/SIMD (80 VGPRs, 68 B of spills): suffix 146.4 -> 143.2 ms per config-M frame; 4 waves 157.8 (r02fc);
+ * 5 waves (no spills) 1480 vs 1510 Msamples/s at 6 (r03m) */
+#define AMVPT_FUSED_WAVES 6
+#endif
+#ifndef AMVPT_FUSED_PARK
+/* path-state groups k_suffix_fused keeps in LDS between the phases that use them (LdsPark) */
+#define AMVPT_FUSED_PARK 0x2f
+#endif
+#ifndef AMVPT_FUSED_WAVES_GLOSSY
+/* the instance with microfacet BSDFs (kDiff = false): its own register budget.  5 waves/SIMD (96 VGPRs, no
+ * scratch) and 6 (80 VGPRs, 44 B of scratch) run the C3 suffix in the same time (305.1 vs 303.9 ms, r04b);
+ * at 6 its PMC bytes are 1.54x the algorithmic ones (r04d_traffic_C3.json), so 5 */
+#define AMVPT_FUSED_WAVES_GLOSSY 5
+#endif
+#ifndef AMVPT_PRIM_HIT_WAVES_DEFER
+#define AMVPT_PRIM_HIT_WAVES_DEFER 8   /* as AMVPT_VIS_WAVES_DEFER, for the primary closest-hit walk */
+#endif
+#ifndef AMVPT_VIS_RAYS
+/* rays per lane of the pair walk.  Not a tunable any more: trace_any2_uni walks two, k_vis asserts the value, and
+ * another one does not build (4 rays measured config-M k_vis 43.5 -> 50.5 ms, C3 165 -> 238 ms, r04z_ab_*.log) */
+#define AMVPT_VIS_RAYS 2
+#endif
+/* waves per SIMD the paired walk's register allocation must allow (0: no bound).  Measured at
+ * config M (r02ac): unbounded 96 VGPRs / 5 waves 69.3 ms, 6 waves (80 VGPRs, 12 B scratch)
+ * 63.5 ms, 8 waves (64 VGPRs, 52 B scratch) 74.1 ms; one ray per lane, 8 waves: 72.3 ms */
+#ifndef AMVPT_VIS_WAVES
+#define AMVPT_VIS_WAVES 6
+#endif
+#ifndef AMVPT_VIS_WAVES_DEFER
+/* k_vis with deferred sphere tests: the walk needs what the sphere-free walk needs (41 VGPRs), so the register
+ * budget is that of 8 waves/SIMD; the float64 tests after the walk -- rare, after the screen -- may spill */
+#define AMVPT_VIS_WAVES_DEFER 8
+#endif
+#ifndef AMVPT_CHUNK_STREAMS
+#define AMVPT_CHUNK_STREAMS 4   /* chunk streams of a per-depth-suffix render (1: every chunk on the render stream; mesh
+                                 * 962-973 / 984-988 / 1001-1002 Msamples/s with 2 / 3 / 4, r05zi) */
+#endif
+#ifndef AMVPT_PRIM_WAVES
+#define AMVPT_PRIM_WAVES 1   /* k_mv_primary's launch bound without the fused vertex: no register cap */
+#endif
+#ifndef AMVPT_PRIM_FUSE_WAVES
+/* waves per SIMD the fused primary vertex's register allocation must allow (kFuse).  Measured at config M, G = 8
+ * (r07a_ab_fused_primary.log): unbounded / 5 waves 87 VGPRs, no scratch, k_mv_primary 74.0 ms per frame; 4 waves
+ * the same; 6 waves (80 VGPRs, 24 B scratch) 71.6 ms; 7 waves (72 VGPRs, 56 B) 73.9 ms; 8 waves 78.2 ms */
+#define AMVPT_PRIM_FUSE_WAVES 6
+#endif
+/* waves per SIMD the register allocation must allow: the 30-KB window admits 5 blocks (20 waves)
+ * per CU, and 5 (<= 96 VGPRs) no longer spills (113.8 vs 117.9 ms per config-M frame, A/B r02z) */
+#ifndef AMVPT_SPLAT_WAVES
+#define AMVPT_SPLAT_WAVES 5
 #endif
 
 namespace amvpt {
@@ -71,14 +176,8 @@ void *g_exchange_ctx = nullptr;
 /* WALK_LANE_TRI: the per-lane walk of a BVH of triangles only (no type dispatch in the leaf tests: the mesh scenes,
  * whose rectangles stay out of the BVH, DScene::outer) */
 enum : int { WALK_LANE = 0, WALK_UNI = 1, WALK_BRUTE = 2, WALK_BRUTE_NS = 3 /* no spheres */, WALK_LANE_NS = 4, WALK_LANE_TRI = 5 };
-#ifndef AMVPT_LANE_TRI
-#define AMVPT_LANE_TRI 1   /* triangle-only BVHs take the WALK_LANE_TRI suffix walks (0: WALK_LANE_NS, A/B) */
-#endif
 /* the per-lane walks' primitive set (dgeom.h trace_closest / trace_any kSph): -1 triangles, 0 no spheres, 1 any */
 template <int kWalk> constexpr int walk_sph() { return kWalk == WALK_LANE_TRI ? -1 : kWalk != WALK_LANE_NS ? 1 : 0; }
-#ifndef AMVPT_LANE_NS
-#define AMVPT_LANE_NS 1   /* sphere-free scenes take the WALK_LANE_NS suffix walks (0: WALK_LANE, A/B) */
-#endif
 /* the per-lane walks take the two-box BVH when the kernel gave the thread a stack (sc.stk: k_extend / k_shadow with
  * KParams::bvh2), else the threaded one */
 template <int kWalk> AD Hit walk_closest(const SceneRef &sc, const Ray &r) {
@@ -89,12 +188,12 @@ template <int kWalk> AD Hit walk_closest(const SceneRef &sc, const Ray &r) {
         outer_closest(sc, r, best, best_orig);
         return trace_closest2<walk_sph<kWalk>()>(sc, r, best, best_orig);
     }
-    return trace_closest<kWalk == WALK_UNI, AMVPT_WALK_WW, walk_sph<kWalk>()>(sc, r);
+    return trace_closest<kWalk == WALK_UNI, 2, walk_sph<kWalk>()>(sc, r);
 }
 template <int kWalk> AD bool walk_any(const SceneRef &sc, const Ray &r) {
     if (kWalk == WALK_BRUTE || kWalk == WALK_BRUTE_NS) return brute_any<kWalk == WALK_BRUTE>(sc, r);
     if (kWalk != WALK_UNI && sc.stk) return trace_any2<walk_sph<kWalk>()>(sc, r, outer_any(sc, r, false));
-    return trace_any<kWalk == WALK_UNI, AMVPT_WALK_WW, walk_sph<kWalk>()>(sc, r);
+    return trace_any<kWalk == WALK_UNI, 2, walk_sph<kWalk>()>(sc, r);
 }
 
 struct KParams {
@@ -137,9 +236,7 @@ struct KParams {
     uint32_t record;      /* write per-lane splat records */
     uint32_t row_splat;   /* row-reduced splat (row_put): lanes in pixel-major order, see slot_lane */
     uint32_t tile_w;      /* != 0: row-splat slots run over 4 x 4 pixel tiles of a tile_w-pixel-wide quilt */
-    /* host-computed reciprocals of the kernel-uniform divisors the path-fetch code divides by (udiv_r; 0 when the
-     * divisor is 0): tile_w / 4, run_len, n_adapt */
-    double rcp_tpr, rcp_run_len, rcp_n_adapt;
+    double reserved[3];   /* keeps the offsets of what follows ("The A/B variants pruned") */
     uint32_t adapt_pass;  /* the suffix runs paths of the adaptive wavefront (path_seq) */
     uint32_t valid_ray0;  /* !hide_emitters && environment: escaped camera rays count as valid
                            * (mvpath_multi.h:140, mvpath_single.h:98, path.cpp:114) */
@@ -204,7 +301,7 @@ struct Bufs {
     uint4 *lmask_w[24];   /* groups > 16 views: valid, indirect, wi.z > 0 masks per slot (mask_planes<G>() each) */
     float *vstate;        /* runtime groups whose per-view state exceeds LDS: VS_FIELDS x G x vs_stride floats */
     float4 *sray[2];      /* ray binning (k_bin_sort): a partition's rays in bin order, 32-B records [2 j], [2 j + 1]:
-                           * extension rays (o, d.x), (d.yz, entry, -); NEE rays (AMVPT_NEE_CARRY) (o, dest),
+                           * extension rays (o, d.x), (d.yz, entry, -); NEE rays (o, dest),
                            * (target, result r) with sgb[j] = result g, b; sray[1] unused */
     float2 *sgb;          /* ray binning of NEE rays: the visible result's green and blue channels in bin order */
     uint16_t *key_out, *key_in, *key_nee;   /* ray binning: bin keys of the pushed paths / NEE records (null: off) */
@@ -230,17 +327,6 @@ __host__ __device__ inline bool scene_staged(uint32_t n_nodes, uint32_t lds_byte
 __host__ __device__ inline uint32_t scene_lds_bytes(const DScene &S, uint32_t mode) {
     return scene_staged(S.n_nodes, S.lds_bytes, mode) ? (S.lds_bytes + 15u) & ~15u : 0u;
 }
-/* the LDS treelet of the first node ordering (any-hit walks of BVHs read from global memory) */
-__host__ __device__ inline uint32_t tree_lds_bytes(const DScene &S, uint32_t mode) {
-    return (S.t_stride && !scene_staged(S.n_nodes, S.lds_bytes, mode) && !scene_uniform(S.n_nodes, mode))
-               ? S.t_stride * (uint32_t) sizeof(DNode) : 0u;
-}
-/* the 8 octant treelets (per-lane closest-hit walks) */
-__host__ __device__ inline uint32_t oct_tree_lds_bytes(const DScene &S, uint32_t mode) {
-    return (S.o_stride && S.oct_stride && !scene_staged(S.n_nodes, S.lds_bytes, mode) && !scene_uniform(S.n_nodes, mode))
-               ? 8u * S.o_stride * (uint32_t) sizeof(DNode) : 0u;
-}
-
 __host__ __device__ inline uint32_t views_lds_bytes(uint32_t n_views) {
     const uint32_t b = n_views * (uint32_t) sizeof(DView);
     return b <= kViewTabBytes ? tab_round(b) : 0u;
@@ -271,7 +357,7 @@ template <typename T> AD T *copy_to_lds(const T *src, uint32_t bytes, char *&dst
  * lane-divergent reads then hit LDS instead of L1/L2.  S is the kernel's local
  * copy of the scene header; its table pointers are redirected.
  */
-template <bool kTab, bool kBvh = true, bool kTree = false, bool kOct = false>
+template <bool kTab, bool kBvh = true>
 AD SceneRef stage_scene(DScene &S, char *lds, uint32_t mode, const DView **V = nullptr, uint32_t n_views = 0,
                         bool boxes = false, bool stage_boxes = false) {
     SceneRef sc;
@@ -288,10 +374,6 @@ AD SceneRef stage_scene(DScene &S, char *lds, uint32_t mode, const DView **V = n
     sc.n_loose_tri = S.n_loose_tri;
     sc.outer = S.outer;   /* every BVH walk tests these (dgeom.h outer_closest / outer_any) */
     sc.n_outer = S.n_outer;
-    sc.tnodes = nullptr;
-    sc.t_n = 0;
-    sc.onodes = nullptr;
-    sc.o_n = 0;
     sc.lds_bvh = false;
     sc.nodes2 = S.n_nodes2 ? S.nodes2 : nullptr;
     sc.stk = nullptr;   /* the two-box walks' stack: set by the kernels that run them (k_extend / k_shadow) */
@@ -315,26 +397,6 @@ AD SceneRef stage_scene(DScene &S, char *lds, uint32_t mode, const DView **V = n
         sc.oct_stride = 0;   /* only the first ordering is staged */
         sc.prims = (const DPrim *) (lds + (size_t) nn * 16);
         dst = lds + scene_lds_bytes(S, mode);
-        sync = true;
-    } else if (kTree && tree_lds_bytes(S, mode)) {
-        /* the treelet of the first node ordering (any-hit walks: trace_any_tl / trace_any_uni_tl) */
-        const uint32_t n4 = S.t_stride * (uint32_t) sizeof(DNode) / 16;
-        float4 *d4 = (float4 *) lds;
-        const float4 *st = (const float4 *) S.tnodes;
-        for (uint32_t i = threadIdx.x; i < n4; i += blockDim.x) d4[i] = st[i];
-        sc.tnodes = (const DNode *) lds;
-        sc.t_n = S.t_stride;
-        dst = lds + tree_lds_bytes(S, mode);
-        sync = true;
-    } else if (kOct && oct_tree_lds_bytes(S, mode)) {
-        /* the 8 octant treelets (closest-hit walks: trace_closest_tl) */
-        const uint32_t n4 = 8u * S.o_stride * (uint32_t) sizeof(DNode) / 16;
-        float4 *d4 = (float4 *) lds;
-        const float4 *st = (const float4 *) S.onodes;
-        for (uint32_t i = threadIdx.x; i < n4; i += blockDim.x) d4[i] = st[i];
-        sc.onodes = (const DNode *) lds;
-        sc.o_n = S.o_stride;
-        dst = lds + oct_tree_lds_bytes(S, mode);
         sync = true;
     }
     /* compile-time choice (the host launches the kTab variant only when the tables fit),
@@ -813,80 +875,23 @@ template <bool kWin = true, bool kDet = true> AD void film_cell_add(const KParam
  * pass; the window is single-buffered (the next put's first barrier orders its
  * adds after this flush), only the tiny bounding-box exchange alternates buffers.
  */
-#ifndef AMVPT_WIN_H
-#define AMVPT_WIN_H 8
-#endif
-#ifndef AMVPT_SPLAT_BLOCK
-#define AMVPT_SPLAT_BLOCK 256
-#endif
-/* Row stride of the window: rows of ww cells are laid out rs cells apart with rs % 32 == 16,
- * so consecutive rows start 32 banks apart for the 64-bit cells (2 * rs mod 64 = 32): lanes
- * whose reprojected footprints straddle a row boundary stop colliding on banks
- * (measured: splat 206 -> 187 ms at config M; rs = ww, or % 32 in {1, 8, 17, 24}: 200-207 ms).
- * The 112-cell width leaves room for the padding (5 blocks per CU either way). */
-/* measurement-only attribution builds (wrong images): 1 skips the LDS adds, 2 the flush's
- * film atomics, 4 the filter weights, 8 turns the LDS atomic adds into plain stores, 16 (with 32:
- * the row-half products too) drops the row splat's cross-lane reduce steps */
-#ifndef AMVPT_ATTR_SKIP
-#define AMVPT_ATTR_SKIP 0
-#endif
-#ifndef AMVPT_WIN_RS
-#define AMVPT_WIN_RS 16
-#endif
-#ifndef AMVPT_WIN_W
-#define AMVPT_WIN_W 112
-#endif
 constexpr int kWinW = AMVPT_WIN_W, kWinH = AMVPT_WIN_H, kMaxWaves = 16, kMaxFoot = 5;
 constexpr int kSplatSuper = 1024;   /* lanes per splat super-block (see slot_lane) */
 constexpr int kSplatBlock = AMVPT_SPLAT_BLOCK;   /* threads per splat block (see slot_lane) */
 constexpr int kWinCells = kWinW * kWinH;
-/*
- * Window cell format.  AMVPT_WIN_FIXED = 0 (default): fp64 cells accumulated with ds_add_f64 --
- * each f32 contribution is exact in f64 and a cell holds at most a few hundred of them, so the
- * window sum is the exact sum to far below the f32 film's resolution.  AMVPT_WIN_FIXED = 1: signed
- * 32.32 fixed point in an int64 word with ds_add_u64 (9.7 lane-ops/clk/CU against 7.5 for
- * ds_add_f64 in isolation, tools/ubench_lds.hip, profiles/r02a_ubench.log; order-independent
- * integer sums, values of magnitude >= 2^20 or non-finite bypass the window) -- but its six-VALU
- * conversion per add costs more than the atomic rate gains now that the row splat is VALU-bound:
- * config-M splat 105.0 ms fixed vs 99.8 ms fp64 (r02fo, r02fp).  AMVPT_WIN_FIXED = 2: fp32 cells
- * with ds_add_f32: 142 ms (the 64-bit bank layout of the row adds no longer spreads).
- */
-#ifndef AMVPT_WIN_FIXED
-#define AMVPT_WIN_FIXED 0
-#endif
-#if AMVPT_WIN_FIXED == 2
-typedef float WinT;        /* fp32 cells, ds_add_f32 (A/B) */
-#elif AMVPT_WIN_FIXED
-typedef long long WinT;
-#else
+/* Window cell format: fp64 cells accumulated with ds_add_f64 -- each f32 contribution is exact in f64 and a
+ * cell holds at most a few hundred of them, so the window sum is the exact sum to far below the f32 film's
+ * resolution. */
 typedef double WinT;
-#endif
-constexpr float kFixMax = 1048576.f;   /* 2^20 */
-/* floor(x * 2^32) as a 64-bit two's-complement word, |x| < 2^31: the high dword is floor(x), the
- * low dword the fraction x - floor(x) (exact) times 2^32, truncated (clamped below 2^32, where a
- * tiny negative x rounds the fraction up to 1) -- six VALU ops, no 64-bit arithmetic */
-AD long long to_fixed(float x) {
-    const float hf = floorf(x);
-    const uint32_t lo = (uint32_t) fminf((x - hf) * 4294967296.f, 4294967040.f);
-    const uint32_t hi = (uint32_t) (int32_t) hf;
-    return (long long) (((unsigned long long) hi << 32) | lo);
-}
-AD float from_fixed(long long q) { return (float) ((double) q * 2.3283064365386963e-10); }
 
 /* channel planes of the window are `plane` cells apart, plane <= kWinPlane (see window_bbox) */
 constexpr int kWinPlane = kWinCells + 32;
 /*
- * AMVPT_WAVE_WIN = 1: the row-reduced splat (row_put) gives every wave a window of its own
+ * The row-reduced splat (row_put) gives every wave a window of its own
  * (kWaveWinW x kWaveWinH cells): a wave's bounding box, adds and flush need no block barrier
  * (LDS operations of one wave complete in order).  A wave = 4 pixels x 16 samples, whose
  * footprints span ~8 x 5 cells (view 0) to ~10 x 6 (reprojected views).
  */
-#ifndef AMVPT_WAVE_WIN
-#define AMVPT_WAVE_WIN 1
-#endif
-#ifndef AMVPT_WAVE_WIN_W
-#define AMVPT_WAVE_WIN_W 32
-#endif
 constexpr int kWaveWinW = AMVPT_WAVE_WIN_W, kWaveWinH = 6, kWavePlane = kWaveWinW * kWaveWinH + 32;
 constexpr int kSplatWaves = AMVPT_SPLAT_BLOCK / 64;
 template <int C> struct SplatLds {
@@ -980,30 +985,7 @@ AD int wave_max(int v) {
 AD void lds_add64(double *p, double v) {
     (void) __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
-/* ds_add_u64, result unused; one window contribution in the cell format */
-AD void lds_add64(long long *p, long long v) {
-    (void) __hip_atomic_fetch_add(reinterpret_cast<unsigned long long *>(p), (unsigned long long) v, __ATOMIC_RELAXED,
-                                  __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-AD void win_add(double *p, float x) {
-    if (AMVPT_ATTR_SKIP & 8) *p = (double) x;   /* attribution: a plain LDS store instead of ds_add_f64 */
-    else lds_add64(p, (double) x);
-}
-AD void win_add(float *p, float x) {
-    (void) __hip_atomic_fetch_add(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-AD void win_add(long long *p, float x) { lds_add64(p, to_fixed(x)); }
-/* may the sample go through the window?  (fixed point: finite and below 2^20 in every channel) */
-template <int C> AD bool win_fits(const float *vals) {
-#if AMVPT_WIN_FIXED == 1
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < C; ++k) ok = ok && fabsf(vals[k]) < kFixMax;
-    return ok;
-#else
-    return true;
-#endif
-}
+AD void win_add(double *p, float x) { lds_add64(p, (double) x); }
 
 /* The block's window: union of the active footprints, clamped to kWinW x kWinH. */
 struct Win { int bx0, by0, ww, wh, rs, plane; };   /* rs: LDS row stride (cells) >= ww; plane >= rs * wh */
@@ -1072,20 +1054,10 @@ AD void window_flush(const KParams &P, float *film, SplatLds<C> &L, const Win &w
         const int r = e - cy * rowlen, cx = r / C, k = r - cx * C;
         WinT *src = win + k * plane + cy * w.rs + cx;
         const WinT d = *src;
-#if AMVPT_WIN_FIXED == 2
-        if (__float_as_int(d) != 0) {
-            *src = 0.f;
-            const float v = d;
-#elif AMVPT_WIN_FIXED
-        if (d != 0) {
-            *src = 0;
-            const float v = from_fixed(d);
-#else
         if (__double_as_longlong(d) != 0ll) {
             *src = 0.0;
             const float v = (float) d;
-#endif
-            if ((v != 0.f || v != v) && !(AMVPT_ATTR_SKIP & 2)) {
+            if (v != 0.f || v != v) {
                 if (inside) film_add(P, film0 + (size_t) cy * film_row + r, v);
                 else film_cell_add(P, film, w.bx0 + cx, w.by0 + cy, k, v);
             }
@@ -1104,7 +1076,7 @@ AD void foot_add(const KParams &P, float *film, WinT *const wbase, const Win &wn
     const bool in_win = cx0 >= wn.bx0 && cy0 >= wn.by0 && f.x0 + f.nx <= wn.bx0 + wn.ww && f.y0 + f.ny <= wn.by0 + wn.wh;
     /* cells per footprint side: uniform over the call (filter radius and method only) */
     const int cnt = P.box ? 1 : (coalesce ? 2 * (int) ceilf(P.filt.radius - .5f) + 1 : (int) ceilf(2.f * P.filt.radius));
-    if (in_win && cnt <= kMaxFoot && win_fits<C>(vals)) {
+    if (in_win && cnt <= kMaxFoot) {
         /* straight-line cnt x cnt cells; clipped cells are masked off (no retry, no branch body) */
         WinT *const c0 = wbase + ((f.y0 - wn.by0) * wn.rs + (f.x0 - wn.bx0));
 #pragma unroll(kRolled ? 1 : kMaxFoot)
@@ -1118,8 +1090,7 @@ AD void foot_add(const KParams &P, float *film, WinT *const wbase, const Win &wn
                     const float w = wx[xs] * wy[ys];
                     WinT *const cp = c0 + ys * wn.rs + xs;
 #pragma unroll
-                    for (int k = 0; k < C; ++k)
-                        if (!(AMVPT_ATTR_SKIP & 1)) win_add(cp + k * plane, P.box ? vals[k] : vals[k] * w);
+                    for (int k = 0; k < C; ++k) win_add(cp + k * plane, P.box ? vals[k] : vals[k] * w);
                 }
             }
         }
@@ -1169,8 +1140,8 @@ AD void direct_put(const KParams &P, float *film, float px, float py, const floa
 template <int kF = FK_LEGACY> AD void foot_weights(const KParams &P, const Foot &f, float *wx, float *wy) {
 #pragma unroll
     for (int t = 0; t < kMaxFoot; ++t) {
-        wx[t] = P.box || (AMVPT_ATTR_SKIP & 4) ? 1.f : feval<kF>(P, f.rx + (float) t);
-        wy[t] = P.box || (AMVPT_ATTR_SKIP & 4) ? 1.f : feval<kF>(P, f.ry + (float) t);
+        wx[t] = P.box ? 1.f : feval<kF>(P, f.rx + (float) t);
+        wy[t] = P.box ? 1.f : feval<kF>(P, f.ry + (float) t);
     }
 }
 
@@ -1179,7 +1150,7 @@ template <int kF = FK_LEGACY> AD void foot_weights(const KParams &P, const Foot 
  * identity), so a DPP row of 16 lanes holds 16 samples of one pixel: for view 0 (coalesced
  * method) the 16 footprints are the same 5 x 5 cells, and a reprojected view's 16 footprints
  * usually fall inside one 6 x 6 box.  When every active footprint of a row lies in the window,
- * the union box of the row is at most 6 x 6 and every value is finite and below kFixMax, the
+ * the union box of the row is at most 6 x 6, the
  * row adds its 16 footprints as ONE reduced 6 x 6 x 4 block: every lane forms its products
  * value_c * (wx * wy) (the reference's per-cell products, imageblock.cpp:265-558) for all 36
  * union cells (zero weight outside its own footprint), and a 4-step reduce-scatter over the row
@@ -1214,17 +1185,6 @@ template <int kF = FK_LEGACY> AD float union_weight(const FilterCoeffs &F, float
     else w = filter_eval_lit<(uint32_t) kF>(r + (float) (cell - x0));
     return (cell >= lo && cell < hi) ? w : 0.f;
 }
-#ifndef AMVPT_SPLAT_PKW
-/* 1: the row splat evaluates its union weights two at a time with packed-f32 operations (gaussian_eval2: the same
- * bits).  Slower (r06ai: splat 78.3 -> 81.7 ms at M, 320 -> 338 ms at C3 -- the scalar form folds every coefficient
- * into v_fmamk / v_fmaak literals, the packed one moves them through registers), so 0: one gaussian_eval per weight */
-#define AMVPT_SPLAT_PKW 0
-#endif
-/* union_weight of cells a and b (packed evaluation) */
-AD f2v_t union_weight2(const FilterCoeffs &F, float r, int x0, int a, int b, int lo, int hi) {
-    const f2v_t w = gaussian_eval2(F, f2v_t{r + (float) (a - x0), r + (float) (b - x0)});
-    return f2v_t{(a >= lo && a < hi) ? w.x : 0.f, (b >= lo && b < hi) ? w.y : 0.f};
-}
 /* The FK_LEGACY row splat runs for the default Gaussian only (rfilter stddev 0.5, the reference's default,
  * gaussian.cpp; the tent, Mitchell and Catmull-Rom row instances hold their defaults' scalars the same way,
  * filter_eval_lit): its coefficients -- exactly what gaussian_coeffs(0.5) computes on the host, checked
@@ -1237,13 +1197,6 @@ AD FilterCoeffs default_filter() {
                         0x1p+1f};
 }
 
-#ifndef AMVPT_SPLAT_SEL
-#define AMVPT_SPLAT_SEL 1   /* row splat: the channel picks as selects on lane masks (0: a pick by lane index, which
-                             * compiled to a branch tree; r05v: splat 85.0 -> 83.3 ms at M, 346.8 -> 343.4 at C3) */
-#endif
-#ifndef AMVPT_SPLAT_PK
-#define AMVPT_SPLAT_PK 1   /* row splat: packed-f32 products of the two row halves: config-M splat 101.8 -> 97.7 ms (r03y; 0: A/B) */
-#endif
 /* union box of the active footprints of the lane's 16-lane row (every lane of the wave active) */
 struct RowBox { int x0, y0, x1, y1; };
 AD RowBox row_box(const Foot &f, bool act) {
@@ -1256,9 +1209,8 @@ AD void row_put_win(const KParams &P, float *film, WinT *const wbase, const Win 
                     const float *vals, bool coalesce, uint32_t *fallback, const RowBox &ub) {
     const int x0c = max(f.x0, 0), y0c = max(f.y0, 0), x1 = f.x0 + f.nx, y1 = f.y0 + f.ny;
     const bool inw = x0c >= wn.bx0 && y0c >= wn.by0 && x1 <= wn.bx0 + wn.ww && y1 <= wn.by0 + wn.wh;
-    const bool good = inw && win_fits<C>(vals);
     const int ux0 = ub.x0, uy0 = ub.y0, ux1 = ub.x1, uy1 = ub.y1;
-    const int bad = row_max((act && !good) ? 1 : 0);
+    const int bad = row_max((act && !inw) ? 1 : 0);
     const bool fast = C == 4 && ux1 > ux0 && bad == 0 && ux1 - ux0 <= 6 && uy1 - uy0 <= 6;
     if (fast) {
         /* every fast row of the wave within 5 union columns / rows (the common case: a coalesced footprint is 5
@@ -1271,7 +1223,6 @@ AD void row_put_win(const KParams &P, float *film, WinT *const wbase, const Win 
         float v[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c) v[c] = act ? vals[c] : 0.f;
-#if AMVPT_SPLAT_SEL
         /* v[ch ^ j] as two selects on lane-constant masks (a pick by a lane-varying index compiled to a
          * branch tree with exec-mask juggling) */
         const bool c0 = (lane & 1) != 0, c1 = (lane & 2) != 0;
@@ -1282,46 +1233,23 @@ AD void row_put_win(const KParams &P, float *film, WinT *const wbase, const Win 
         };
         const float K = pick(0);
         const float B1 = dpp_f<DPP_XOR1>(pick(1)), B2 = dpp_f<DPP_XOR2>(pick(2)), B3 = dpp_f<DPP_XOR3>(pick(3));
-#else
-        auto pick = [&](int c) { return c == 0 ? v[0] : c == 1 ? v[1] : c == 2 ? v[2] : v[3]; };
-        /* K: this lane's value of its channel; Bj: the value of this lane's channel at quad lane
-         * (lane ^ j), which hands over its own v[ch ^ j] */
-        const float K = pick(ch);
-        const float B1 = dpp_f<DPP_XOR1>(pick(ch ^ 1)), B2 = dpp_f<DPP_XOR2>(pick(ch ^ 2)),
-                    B3 = dpp_f<DPP_XOR3>(pick(ch ^ 3));
-#endif
         /* inactive lanes hand over v = 0, so their (finite) weights need no masking: the weights are
          * straight-line code, not a branch per evaluation */
         const FilterCoeffs F = default_filter();
         float wx[6];
-#if AMVPT_SPLAT_PKW
-#pragma unroll
-        for (int c = 0; c < 6; c += 2) {
-            const f2v_t w = union_weight2(F, f.rx, f.x0, ux0 + c, ux0 + c + 1, x0c, x1);
-            wx[c] = w.x;
-            wx[c + 1] = w.y;
-        }
-        if (u5) wx[5] = 0.f;
-#else
 #pragma unroll
         for (int c = 0; c < 5; ++c) wx[c] = union_weight<kF>(F, f.rx, f.x0, ux0 + c, x0c, x1);
         wx[5] = 0.f;
         if (!u5) wx[5] = union_weight<kF>(F, f.rx, f.x0, ux0 + 5, x0c, x1);
-#endif
         WinT *const wch = wbase + ch * wn.plane;
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
             /* row position r + 3 h holds union row r + 3 (h ^ b2); the quad shares b2 */
             float Ky[2], B1y[2], B2y[2], B3y[2];
             /* union rows r and r + 3 (lane-uniform), row 5 skipped when every fast row of the wave fits 5 */
-#if AMVPT_SPLAT_PKW
-            const f2v_t wyAB = union_weight2(F, f.ry, f.y0, uy0 + r, uy0 + r + 3, y0c, y1);
-            const float wyA = wyAB.x, wyB = (r < 2 || !u5r) ? wyAB.y : 0.f;
-#else
             const float wyA = union_weight<kF>(F, f.ry, f.y0, uy0 + r, y0c, y1);
             float wyB = 0.f;
             if (r < 2 || !u5r) wyB = union_weight<kF>(F, f.ry, f.y0, uy0 + r + 3, y0c, y1);
-#endif
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const float wy = (h ^ b2) ? wyB : wyA;
@@ -1333,7 +1261,6 @@ AD void row_put_win(const KParams &P, float *film, WinT *const wbase, const Win 
             /* steps 1-2: the quad's sum of this lane's channel, sum_j v_j[ch] wy_j wx_j; step 3: plus
              * the rotate-4 partner's quad sum of the other row half */
             float z[6];
-#if AMVPT_SPLAT_PK
             /* the two row halves as one packed pair (v_pk_mul_f32 / v_pk_fma_f32: per-element IEEE, the
              * same products and sums bit for bit) */
             typedef float f2v __attribute__((ext_vector_type(2)));
@@ -1349,27 +1276,13 @@ AD void row_put_win(const KParams &P, float *film, WinT *const wbase, const Win 
             for (int c = 0; c < 5; ++c) z[c] = col(c);
             z[5] = 0.f;
             if (!u5) z[5] = col(5);
-#else
-#pragma unroll
-            for (int c = 0; c < 6; ++c) {
-                float y[2];
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    float a = Ky[h] * wx[c];
-                    a = fmaf(dpp_f<DPP_XOR1>(wx[c]), B1y[h], a);
-                    a = fmaf(dpp_f<DPP_XOR2>(wx[c]), B2y[h], a);
-                    y[h] = fmaf(dpp_f<DPP_XOR3>(wx[c]), B3y[h], a);
-                }
-                z[c] = y[0] + dpp_f<DPP_ROR4>(y[1]);
-            }
-#endif
             const int row = r + 3 * b2;
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const float keep = b3 ? z[c + 3] : z[c], send = b3 ? z[c] : z[c + 3];
-                const float u = (AMVPT_ATTR_SKIP & 16) ? z[c] : keep + dpp_f<DPP_ROR8>(send);
+                const float u = keep + dpp_f<DPP_ROR8>(send);
                 const int col = c + 3 * b3;
-                if (ux0 + col < ux1 && uy0 + row < uy1 && !(AMVPT_ATTR_SKIP & 1))
+                if (ux0 + col < ux1 && uy0 + row < uy1)
                     win_add(wch + (uy0 + row - wn.by0) * wn.rs + (ux0 + col - wn.bx0), u);
             }
         }
@@ -1402,20 +1315,10 @@ AD void wave_flush(const KParams &P, float *film, WinT *win, const Win &w) {
         const int r = e - cy * rowlen, cx = r / C, k = r - cx * C;
         WinT *src = win + k * w.plane + cy * w.rs + cx;
         const WinT d = *src;
-#if AMVPT_WIN_FIXED == 2
-        if (__float_as_int(d) != 0) {
-            *src = 0.f;
-            const float v = d;
-#elif AMVPT_WIN_FIXED
-        if (d != 0) {
-            *src = 0;
-            const float v = from_fixed(d);
-#else
         if (__double_as_longlong(d) != 0ll) {
             *src = 0.0;
             const float v = (float) d;
-#endif
-            if ((v != 0.f || v != v) && !(AMVPT_ATTR_SKIP & 2)) {
+            if (v != 0.f || v != v) {
                 if (inside) atomicAdd(film0 + ((uint32_t) cy * film_row + (uint32_t) r), v);   /* never deterministic */
                 else film_cell_add<kWin, false>(P, film, w.bx0 + cx, w.by0 + cy, k, v);
             }
@@ -1424,7 +1327,7 @@ AD void wave_flush(const KParams &P, float *film, WinT *win, const Win &w) {
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
 }
 
-/* ImageBlock::put of a wave's samples through its own window (AMVPT_WAVE_WIN, row_splat) */
+/* ImageBlock::put of a wave's samples through its own window (row_splat) */
 template <int C, bool kWin = true, int kF = FK_LEGACY>
 AD void wave_put(const KParams &P, float *film, WaveLds<C> &L, float px, float py, const float *vals, bool valid,
                  bool coalesce, uint32_t *fallback) {
@@ -1507,43 +1410,19 @@ AD void block_put(const KParams &P, float *film, SplatLds<C> &L, int buf, float 
 constexpr int kSplatSplit = kSplatSuper / kSplatBlock;
 constexpr uint32_t kSplatSuperLog = __builtin_ctz(kSplatSuper), kSplatSplitLog = __builtin_ctz(kSplatSplit);
 static_assert((1 << kSplatSuperLog) == kSplatSuper && (1 << kSplatSplitLog) == kSplatSplit, "powers of two");
-#ifndef AMVPT_UDIV_RCP
-/* 1: the path fetch of the suffix kernels (path_seq: slot -> lane -> TEA seed) divides by its kernel-uniform runtime
- * divisors through host-computed f64 reciprocals (udiv_r<true>) -- the generic expansion computes each divisor's
- * reciprocal in VGPRs up front, and the fused suffix spilled three of them (a scratch reload and wait at every path
- * fetch).  Elsewhere (k_mv_primary's slot order, the splat) the plain division stays: there the f64 form cost more
- * than it saved (r06am: config-M k_mv_primary 39.7 -> 41.6 ms).  The path-fetch form measured neutral (r06an: M, mesh
- * and C5 within noise, the reloads hide behind the other waves), so 0: plain division everywhere */
-#define AMVPT_UDIV_RCP 0
-#endif
-/* n / d for a kernel-uniform d > 0, exactly: the f64 product n * fl(1/d) lies within 2^-20 of n / d (n, d < 2^32),
- * so its truncation is the quotient or one off, and one step each way corrects it */
-template <bool kRcp = true> AD uint32_t udiv_r(uint32_t n, uint32_t d, double rcp) {
-    if (!(AMVPT_UDIV_RCP && kRcp)) return n / d;
-    uint32_t q = (uint32_t) ((double) n * rcp);
-    q -= ((uint64_t) q * d > (uint64_t) n) ? 1u : 0u;
-    q += ((uint64_t) (q + 1u) * d <= (uint64_t) n) ? 1u : 0u;
-    return q;
-}
-/* host side of udiv_r */
-inline double host_rcp(uint32_t d) { return d ? 1.0 / (double) d : 0.0; }
 /*
  * Tiled slot order (KParams::tile_w, 16 samples per pixel and pass): slot block b of 256 = the 4 x 4
  * pixel tile b of the chunk's rows (tile rows of tile_w / 4 tiles), a wave = one pixel row of the
  * tile (64 consecutive lanes), a DPP row = one pixel.  A splat block's footprints then cover ~8 x 8
  * cells instead of 20 x 5, so a block-wide window flushes fewer film cells per sample.
  */
-template <bool kRcp = false> AD uint32_t tile_slot_lane(const KParams &P, uint32_t slot) {
+AD uint32_t tile_slot_lane(const KParams &P, uint32_t slot) {
     const uint32_t b = slot >> 8, t = slot & 255u, tpr = P.tile_w >> 2;
-    const uint32_t trow = udiv_r<kRcp>(b, tpr, P.rcp_tpr), tcol = b - trow * tpr, pt = t >> 4;
+    const uint32_t trow = b / tpr, tcol = b - trow * tpr, pt = t >> 4;
     return ((trow * 4u + (pt >> 2)) * P.tile_w + tcol * 4u + (pt & 3u)) * 16u + (t & 15u);
 }
-AD uint32_t tile_lane_slot(const KParams &P, uint32_t lane) {
-    const uint32_t pix = lane >> 4, y = pix / P.tile_w, x = pix - y * P.tile_w, tpr = P.tile_w >> 2;
-    return (((y >> 2) * tpr + (x >> 2)) << 8) | ((((y & 3u) << 2) | (x & 3u)) << 4) | (lane & 15u);
-}
-template <bool kRcp = false> AD uint32_t slot_lane(const KParams &P, uint32_t slot) {
-    if (P.tile_w) return tile_slot_lane<kRcp>(P, slot);
+AD uint32_t slot_lane(const KParams &P, uint32_t slot) {
+    if (P.tile_w) return tile_slot_lane(P, slot);
     if (P.row_splat) return slot;   /* pixel-major: a 16-lane row = 16 samples of one pixel (row_put) */
     const uint32_t super = slot / (uint32_t) kSplatSuper, within = slot % (uint32_t) kSplatSuper;
     const uint32_t base = super * kSplatSuper;
@@ -1555,21 +1434,6 @@ template <bool kRcp = false> AD uint32_t slot_lane(const KParams &P, uint32_t sl
         return base + (t & (ppb - 1u)) * S + h * (S / kSplatSplit) + (t >> (kSplatSuperLog - P.log_spp));
     }
     return slot;
-}
-/* inverse of slot_lane */
-AD uint32_t lane_slot(const KParams &P, uint32_t lane) {
-    if (P.tile_w) return tile_lane_slot(P, lane);
-    if (P.row_splat) return lane;
-    const uint32_t super = lane / (uint32_t) kSplatSuper, off = lane % (uint32_t) kSplatSuper;
-    const uint32_t base = super * kSplatSuper;
-    const uint32_t remain = P.chunk_n > base ? P.chunk_n - base : 0;
-    const uint32_t S = P.spp_pp;
-    if (remain >= (uint32_t) kSplatSuper && P.pow2 && S >= (uint32_t) kSplatSplit && S <= (uint32_t) kSplatBlock) {
-        const uint32_t half = S / kSplatSplit, ppb = (uint32_t) kSplatSuper >> P.log_spp;
-        const uint32_t p = off >> P.log_spp, smp = off & (S - 1u);
-        return base + (smp >> (P.log_spp - kSplatSplitLog)) * (uint32_t) kSplatBlock + (smp & (half - 1u)) * ppb + p;
-    }
-    return lane;
 }
 
 /* ImageBlock::put's sample check (imageblock.cpp:180-204: warn_invalid / warn_negative): an active
@@ -1668,25 +1532,8 @@ struct PathState {
  */
 /* the bin key of a ray (ray binning, k_bin_sort): direction octant (major) and the Morton code of the
  * origin's cell in a 2^kBinCellBits-per-axis grid over the scene box */
-#ifndef AMVPT_BIN_CELL_BITS
-#define AMVPT_BIN_CELL_BITS 2   /* origin cells per axis of the bin key: 2^bits; 3 (4096 keys): walks 3 ms faster, sort 16 ms slower (r05d) */
-#endif
 constexpr uint32_t kBinCellBits = AMVPT_BIN_CELL_BITS, kBins = 8u << (3 * kBinCellBits), kBinBlock = 1024;
-#ifndef AMVPT_BIN_UNROLL
-#define AMVPT_BIN_UNROLL 4   /* entries per thread in flight in k_bin_sort's passes (one 1024-thread block per partition) */
-#endif
 constexpr uint32_t kBinUnroll = AMVPT_BIN_UNROLL;
-#ifndef AMVPT_BIN_PREFETCH
-/* 1: k_bin_sort's staged scatter loads the next batch during this one's run writes.  Neutral (r06af: k_bin 50.4 ms
- * either way on one box), so 0.  The same change holds the entries in named structs instead of arrays indexed by an
- * unrolled loop, which the compiler had promoted to 32 KB of LDS (each load then waited for its LDS copy): k_bin
- * 57.8 -> 56.9 ms per mesh frame on one box (r06ah; k_bin differs by up to 7 ms between boxes) */
-#define AMVPT_BIN_PREFETCH 0
-#endif
-#ifndef AMVPT_BIN_STAGE
-#define AMVPT_BIN_STAGE 1   /* k_bin_sort stages each batch in LDS and writes runs of one bin: sort 54.0 -> 50.3 ms,
-                                     * mesh 857 -> 876 Msamples/s (r05h); 0: one scattered write per entry (A/B) */
-#endif
 AD uint32_t bin_key(const KParams &P, f3 o, f3 d) {
     const uint32_t oct = (fbits(d.x) >> 31) | ((fbits(d.y) >> 31) << 1) | ((fbits(d.z) >> 31) << 2);
     auto cell = [&](float v, int a) {
@@ -1745,17 +1592,17 @@ AD PathState load_state(float4 *const *q, uint32_t slot) {
 
 /* global lane (mvpath.cpp:173-190 wavefront index) of virtual index v of the render's lane set:
  * a contiguous range, or rect_h runs of run_len lanes (one per pixel row of the rectangle) */
-template <bool kRcp = false> AD uint32_t lane_of(const KParams &P, uint64_t v) {
+AD uint32_t lane_of(const KParams &P, uint64_t v) {
     if (!P.rect) return (uint32_t) (P.range_begin + v);
-    const uint32_t vv = (uint32_t) v, r = udiv_r<kRcp>(vv, P.run_len, P.rcp_run_len), o = vv - r * P.run_len;
+    const uint32_t vv = (uint32_t) v, r = vv / P.run_len, o = vv - r * P.run_len;
     return ((P.rect_y0 + r) * P.W + P.rect_x0) * P.spp_pp + o;
 }
 /* the adaptive fill (mvpath_multi.h:79-115: dr::compress, dr::repeat): index in the PASS's
  * repeated wavefront of entry j of this render's part -- entry e = j / n_adapt of the render's
  * compressed list sits at e + run_delta[run of its lane] of the pass's compressed array */
-template <bool kRcp = false> AD uint32_t adapt_index(const KParams &P, const Bufs &B, uint32_t j) {
-    const uint32_t e = udiv_r<kRcp>(j, P.n_adapt, P.rcp_n_adapt), rep = j - e * P.n_adapt;
-    const uint32_t run = P.rect ? udiv_r<kRcp>(B.asel[e], P.run_len, P.rcp_run_len) : 0u;
+AD uint32_t adapt_index(const KParams &P, const Bufs &B, uint32_t j) {
+    const uint32_t e = j / P.n_adapt, rep = j - e * P.n_adapt;
+    const uint32_t run = P.rect ? B.asel[e] / P.run_len : 0u;
     return (e + B.run_delta[run]) * P.n_adapt + rep;
 }
 
@@ -1764,8 +1611,8 @@ template <bool kRcp = false> AD uint32_t adapt_index(const KParams &P, const Buf
  * the adaptive pass wavefront entry chunk_begin + slot with adapt_seed (k_raygen_adapt) */
 AD uint32_t path_seq(const KParams &P, const Bufs &B, uint32_t slot) {
     uint32_t v0, v1;
-    if (P.adapt_pass) tea4(P.adapt_seed, adapt_index<true>(P, B, (uint32_t) (P.chunk_begin + slot)), v0, v1);
-    else tea4(P.seed_value, lane_of<true>(P, P.chunk_begin + slot_lane<true>(P, slot)), v0, v1);
+    if (P.adapt_pass) tea4(P.adapt_seed, adapt_index(P, B, (uint32_t) (P.chunk_begin + slot)), v0, v1);
+    else tea4(P.seed_value, lane_of(P, P.chunk_begin + slot_lane(P, slot)), v0, v1);
     return v1;
 }
 
@@ -1879,36 +1726,6 @@ AMVPT_TU_LOCAL __global__ void __launch_bounds__(256) k_raygen_adapt(KParams P, 
  * The accumulation order of a lane's result is the reference's: emitter hit of
  * vertex d, then NEE of vertex d, then vertex d + 1.
  */
-/* waves per SIMD the suffix walks' register allocation must allow (latency-bound dependent node loads):
- * k_extend at 6 (80 VGPRs) took the mesh frame 599 -> 609 Msamples/s; 8 (64 VGPRs, 48 B of spills)
- * 606; k_shadow keeps its own allocation (r03k) */
-#ifndef AMVPT_EXTEND_WAVES
-#define AMVPT_EXTEND_WAVES 6
-#endif
-#ifndef AMVPT_TREELETS
-/* walks of large BVHs that start in an LDS treelet: bit 0 k_shadow (per-lane any hit), bit 1 k_extend (per-lane
- * closest hit, octant treelets), bit 2 k_vis (wave-uniform any hit).  Off: measured slower on the mesh bench
- * (r04c, one-stream kernel ms: k_extend 266 -> 320, k_shadow 191 -> 254, k_vis 80 -> 110; 717 -> 634 / 607
- * Msamples/s) -- the top levels they stage are the nodes every walk already finds in L1 / the scalar cache,
- * and a wave whose lanes are split between treelet and global nodes waits for both loads per step. */
-#define AMVPT_TREELETS 0
-#endif
-#ifndef AMVPT_EXTEND_RAYS
-/* per-lane k_extend walks: paths per thread (2: trace_closest_lane2, A/B).  1: the two-path walk measured slower
- * on the mesh bench (k_extend 229.4 -> 254.9 ms at 5 waves/SIMD, r04z_ab_mesh.log) */
-#define AMVPT_EXTEND_RAYS 1
-#endif
-#ifndef AMVPT_EXTEND2_WAVES
-#define AMVPT_EXTEND2_WAVES 5   /* the two-path walk: 89 VGPRs, no scratch (at 6: 80 VGPRs and spills inside the walk) */
-#endif
-#ifndef AMVPT_SHADOW_RAYS
-/* per-lane k_shadow walks: records per thread (2: trace_any_lane2, A/B).  1: k_shadow 172.8 -> 182.7 ms with two
- * (r04z_ab_mesh.log) */
-#define AMVPT_SHADOW_RAYS 1
-#endif
-#ifndef AMVPT_SHADOW_WAVES
-#define AMVPT_SHADOW_WAVES 1
-#endif
 /*
  * Ray binning for the per-lane suffix walks of large BVHs (coherence, not more per-lane tricks).
  * The suffix rays of a queue partition arrive in whatever order the producer blocks pushed them: neighbouring
@@ -1923,23 +1740,13 @@ AMVPT_TU_LOCAL __global__ void __launch_bounds__(256) k_raygen_adapt(KParams P, 
  * each ray does not depend on which lane walks it, so records stay bit-identical.  NEE rays are keyed the
  * same way (direction to the light sample).
  */
-#ifndef AMVPT_BIN
-#define AMVPT_BIN 3   /* bit 0: bin the extension rays (k_extend), bit 1: the NEE rays (k_shadow); 0: off (A/B) */
-#endif
-#ifndef AMVPT_NEE_CARRY
-/* 1: a binned NEE record carries the visible result itself (red in the record's last word, green and blue in a
- * bin-order plane, sgb) instead of the entry it came from: k_shadow's visible write then reads it with the sorted
- * record (coalesced) instead of two scattered loads from the unsorted records (nee[1][entry].w, nee_gb[entry]) --
- * the mesh frame's k_shadow fetched 270 GB from HBM for ~50 GB of sorted records (r06y_traffic_mesh.json); 0: A/B */
-#define AMVPT_NEE_CARRY 1
-#endif
-#ifndef AMVPT_BIN_UNI
-#define AMVPT_BIN_UNI 0   /* 1: binned waves take the wave-uniform walk (scalar node loads) instead of the per-lane one */
-#endif
 template <bool kNee, bool kFromRays = false>
 __global__ void __launch_bounds__(kBinBlock) k_bin_sort(KParams P, Bufs B) {
-    /* NEE records carry their visible result (AMVPT_NEE_CARRY): k_shadow then reads it in bin order */
-    constexpr bool nee_carry = kNee && AMVPT_NEE_CARRY;
+    /* a binned NEE record carries the visible result itself (red in the record's last word, green and blue in a
+     * bin-order plane, sgb), not the entry it came from: k_shadow's visible write then reads it with the sorted record
+     * (coalesced) instead of two scattered loads from the unsorted records -- the mesh frame's k_shadow had fetched
+     * 270 GB from HBM for ~50 GB of sorted records (r06y_traffic_mesh.json) */
+    constexpr bool nee_carry = kNee;
     __shared__ uint32_t h[kBins];
     __shared__ uint32_t wsum[kBinBlock / 64];
     const uint32_t part = blockIdx.x;
@@ -1994,26 +1801,16 @@ __global__ void __launch_bounds__(kBinBlock) k_bin_sort(KParams P, Bufs B) {
         run += v[k];
     }
     __syncthreads();
-    /* the scatter, two entries per thread in flight: each ray (32 B) to its bin's next position */
-    auto place = [&](uint32_t i, const float4 &a, const float4 &b, uint32_t key) {
-        /* one 32-B record per ray (a whole memory sector per scattered write, not two 16-B halves in two planes) */
-        const uint32_t j = pbase + atomicAdd(&h[key], 1u);
-        B.sray[0][2 * (size_t) j] = a;
-        B.sray[0][2 * (size_t) j + 1] = nee_carry ? b : kNee ? make_float4(b.x, b.y, b.z, bitsf(i)) : make_float4(b.x, b.y, bitsf(i), 0.f);
-        if (nee_carry) B.sgb[j] = B.nee_gb[i];
-    };
-#if AMVPT_BIN_STAGE
     /* staged scatter: batches of kStage entries are counting-sorted in LDS first, so the global writes go out
      * as runs of consecutive records of one bin (consecutive threads, consecutive addresses) */
     constexpr uint32_t kStage = 2 * kBinBlock;
     __shared__ float4 stg[2 * kStage];
-    __shared__ float2 sgb[kNee && AMVPT_NEE_CARRY ? kStage : 1];
+    __shared__ float2 sgb[kNee ? kStage : 1];
     __shared__ uint16_t skey[kStage];
     __shared__ uint32_t lh[kBins], lbase[kBins];
-    /* the batch's global loads (rays, producer keys, carried green / blue): with AMVPT_BIN_PREFETCH the next batch's
-     * are issued before this batch's run writes, so their latency overlaps them (one block per CU leaves nothing
-     * else to hide it).  Two entries per thread as named structs, not arrays: an array indexed by the unrolled
-     * entry loop is promoted to LDS before the loop is unrolled, and the load then waits for its LDS copy. */
+    /* the batch's global loads (rays, producer keys, carried green / blue).  Two entries per thread as named structs,
+     * not arrays: an array indexed by the unrolled entry loop is promoted to LDS before the loop is unrolled, and the
+     * load then waits for its LDS copy: k_bin 57.8 -> 56.9 ms per mesh frame on one box (r06ah) */
     struct Ent { float4 a, b; uint32_t k, r; float2 g; };
     auto load = [&](uint32_t e, Ent &x) {
         const uint32_t i = pbase + min(e, count - 1u);
@@ -2021,15 +1818,15 @@ __global__ void __launch_bounds__(kBinBlock) k_bin_sort(KParams P, Bufs B) {
         if (!kFromRays) x.k = keys[i];
         if (nee_carry) x.g = B.nee_gb[i];
     };
-    Ent x0, x1, n0, n1;
-    x0.k = x1.k = n0.k = n1.k = 0u;
-    x0.g = x1.g = n0.g = n1.g = make_float2(0.f, 0.f);
-    if (AMVPT_BIN_PREFETCH && count > 0) { load(threadIdx.x, x0); load(threadIdx.x + kBinBlock, x1); }
+    Ent x0, x1;
+    x0.k = x1.k = 0u;
+    x0.g = x1.g = make_float2(0.f, 0.f);
     for (uint32_t b0 = 0; b0 < count; b0 += kStage) {
         const uint32_t n = min(kStage, count - b0);
         for (uint32_t q = threadIdx.x; q < kBins; q += kBinBlock) lh[q] = 0u;
         __syncthreads();
-        if (!AMVPT_BIN_PREFETCH) { load(b0 + threadIdx.x, x0); load(b0 + threadIdx.x + kBinBlock, x1); }
+        load(b0 + threadIdx.x, x0);
+        load(b0 + threadIdx.x + kBinBlock, x1);
         auto rank = [&](Ent &x, uint32_t e) {
             if (kFromRays) x.k = bin_key(P, mk(x.a.x, x.a.y, x.a.z), mk(x.a.w, x.b.x, x.b.y));
             x.r = e < count ? atomicAdd(&lh[x.k], 1u) : 0u;
@@ -2069,16 +1866,13 @@ __global__ void __launch_bounds__(kBinBlock) k_bin_sort(KParams P, Bufs B) {
             if (e < count) {
                 const uint32_t sp = lh[x.k] + x.r, i = pbase + e;
                 stg[2 * sp] = x.a;
-                stg[2 * sp + 1] = nee_carry ? x.b : kNee ? make_float4(x.b.x, x.b.y, x.b.z, bitsf(i)) : make_float4(x.b.x, x.b.y, bitsf(i), 0.f);
+                stg[2 * sp + 1] = nee_carry ? x.b : make_float4(x.b.x, x.b.y, bitsf(i), 0.f);
                 if (nee_carry) sgb[sp] = x.g;
                 skey[sp] = (uint16_t) x.k;
             }
         };
         stage(x0, b0 + threadIdx.x);
         stage(x1, b0 + threadIdx.x + kBinBlock);
-        /* the next batch's loads (registers of their own, live across the run writes) */
-        const bool more = AMVPT_BIN_PREFETCH && b0 + kStage < count;
-        if (more) { load(b0 + kStage + threadIdx.x, n0); load(b0 + kStage + threadIdx.x + kBinBlock, n1); }
         __syncthreads();
         for (uint32_t sp = threadIdx.x; sp < n; sp += kBinBlock) {
             const uint32_t q = skey[sp], j = pbase + lbase[q] + (sp - lh[q]);
@@ -2086,33 +1880,15 @@ __global__ void __launch_bounds__(kBinBlock) k_bin_sort(KParams P, Bufs B) {
             B.sray[0][2 * (size_t) j + 1] = stg[2 * sp + 1];
             if (nee_carry) B.sgb[j] = sgb[sp];
         }
-        if (more) { x0 = n0; x1 = n1; }
         __syncthreads();
     }
-#else
-    for (uint32_t e0 = threadIdx.x; e0 < count; e0 += kBinUnroll * kBinBlock) {
-        float4 a[kBinUnroll], b[kBinUnroll];
-        uint32_t k[kBinUnroll];
-#pragma unroll
-        for (uint32_t u = 0; u < kBinUnroll; ++u) {
-            const uint32_t e = min(e0 + u * kBinBlock, count - 1u), i = pbase + e;
-            a[u] = src[0][i]; b[u] = src[1][i];
-            k[u] = kFromRays ? bin_key(P, mk(a[u].x, a[u].y, a[u].z), mk(a[u].w, b[u].x, b[u].y)) : keys[i];
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < kBinUnroll; ++u)
-            if (e0 + u * kBinBlock < count) place(pbase + e0 + u * kBinBlock, a[u], b[u], k[u]);
-    }
-#endif
 }
 
 template <int kWalk, bool kBin = false>
-__global__ void __launch_bounds__(256, (AMVPT_EXTEND_RAYS == 2 && (kWalk == WALK_LANE || kWalk == WALK_LANE_NS)) ? AMVPT_EXTEND2_WAVES
-                                                                                                                  : AMVPT_EXTEND_WAVES)
-k_extend(KParams P, const DScene *Sp, Bufs B) {
+__global__ void __launch_bounds__(256, AMVPT_EXTEND_WAVES) k_extend(KParams P, const DScene *Sp, Bufs B) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     DScene S = *Sp;
-    SceneRef sc = stage_scene<false, true, false, (AMVPT_TREELETS & 2) != 0>(S, lds, P.trav_mode, nullptr, 0, P.box_screen != 0);
+    SceneRef sc = stage_scene<false>(S, lds, P.trav_mode, nullptr, 0, P.box_screen != 0);
     if (P.bvh2) sc.stk = reinterpret_cast<uint32_t *>(lds + P.stk_off_ext) + threadIdx.x;
     const uint32_t part = blockIdx.x % kQParts, pstride = gridDim.x / kQParts * blockDim.x;
     const uint32_t count = B.cnt_in[part * kCntStride], pbase = part * B.qcap;
@@ -2127,24 +1903,8 @@ k_extend(KParams P, const DScene *Sp, Bufs B) {
             if (e0 + threadIdx.x < count) {
                 const float4 a = B.sray[0][2 * (size_t) j], b = B.sray[0][2 * (size_t) j + 1];
                 const Ray r{mk(a.x, a.y, a.z), mk(a.w, b.x, b.y), kLargest};
-                const Hit h = AMVPT_BIN_UNI ? trace_closest<true, 0, kWalk != WALK_LANE_NS>(sc, r) : walk_closest<kWalk>(sc, r);
-                B.hit[fbits(b.z)] = hit_rec(h);
+                B.hit[fbits(b.z)] = hit_rec(walk_closest<kWalk>(sc, r));
             }
-        }
-        return;
-    }
-    if constexpr (AMVPT_EXTEND_RAYS == 2 && (kWalk == WALK_LANE || kWalk == WALK_LANE_NS)) {
-        /* two paths per thread (trace_closest_lane2): entries e0 + t and e0 + t + blockDim.x */
-        for (uint32_t e0 = blockIdx.x / kQParts * 2u * blockDim.x; e0 < count; e0 += 2u * pstride) {
-            const uint32_t e_0 = e0 + threadIdx.x, e_1 = e_0 + blockDim.x;
-            const bool act0 = e_0 < count, act1 = e_1 < count;
-            Ray r0{mk(0.f, 0.f, 0.f), mk(0.f, 0.f, 1.f), kLargest}, r1 = r0;
-            if (act0) { const float4 a = B.q_in[0][pbase + e_0], b = B.q_in[1][pbase + e_0]; r0 = Ray{mk(a.x, a.y, a.z), mk(a.w, b.x, b.y), kLargest}; }
-            if (act1) { const float4 a = B.q_in[0][pbase + e_1], b = B.q_in[1][pbase + e_1]; r1 = Ray{mk(a.x, a.y, a.z), mk(a.w, b.x, b.y), kLargest}; }
-            Hit h0, h1;
-            trace_closest_lane2<kWalk == WALK_LANE_NS ? 0 : 1>(sc, r0, act0, r1, act1, h0, h1);
-            if (act0) B.hit[pbase + e_0] = hit_rec(h0);
-            if (act1) B.hit[pbase + e_1] = hit_rec(h1);
         }
         return;
     }
@@ -2162,7 +1922,7 @@ template <int kWalk, bool kBin = false>
 __global__ void __launch_bounds__(256, AMVPT_SHADOW_WAVES) k_shadow(KParams P, const DScene *Sp, Bufs B) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     DScene S = *Sp;
-    SceneRef sc = stage_scene<false, true, (AMVPT_TREELETS & 1) != 0>(S, lds, P.trav_mode, nullptr, 0, P.box_screen != 0);
+    SceneRef sc = stage_scene<false>(S, lds, P.trav_mode, nullptr, 0, P.box_screen != 0);
     if (P.bvh2) sc.stk = reinterpret_cast<uint32_t *>(lds + P.stk_off_any) + threadIdx.x;
     const uint32_t part = blockIdx.x % kQParts, pstride = gridDim.x / kQParts * blockDim.x;
     const uint32_t count = B.cnt_nee[part * kCntStride], pbase = part * B.qcap;
@@ -2192,37 +1952,16 @@ __global__ void __launch_bounds__(256, AMVPT_SHADOW_WAVES) k_shadow(KParams P, c
             if (e0 + threadIdx.x < count) {
                 const float4 a = B.sray[0][2 * (size_t) j], b = B.sray[0][2 * (size_t) j + 1];
                 const Ray r = nee_ray(a, b);
-                const bool occ = AMVPT_BIN_UNI ? trace_any<true, 0, kWalk != WALK_LANE_NS>(sc, r) : walk_any<kWalk>(sc, r);
-                if (!occ) {
-                    if (AMVPT_NEE_CARRY) {
-                        /* the record's own result: red in b.w, green and blue in sgb[j] */
-                        const float2 gb = B.sgb[j];
-                        const uint32_t dest = fbits(a.w);
-                        float *const dp = (float *) ((dest & 0x80000000u) ? &B.lane_out[dest & 0x7fffffffu] : &B.q_out[4][dest]);
-                        dp[0] = b.w;
-                        dp[1] = gb.x;
-                        dp[2] = gb.y;
-                    } else {
-                        const uint32_t i = fbits(b.w);
-                        visible(i, a, make_float4(0.f, 0.f, 0.f, B.nee[1][i].w));
-                    }
+                if (!walk_any<kWalk>(sc, r)) {
+                    /* the record's own result: red in b.w, green and blue in sgb[j] */
+                    const float2 gb = B.sgb[j];
+                    const uint32_t dest = fbits(a.w);
+                    float *const dp = (float *) ((dest & 0x80000000u) ? &B.lane_out[dest & 0x7fffffffu] : &B.q_out[4][dest]);
+                    dp[0] = b.w;
+                    dp[1] = gb.x;
+                    dp[2] = gb.y;
                 }
             }
-        }
-        return;
-    }
-    if constexpr (AMVPT_SHADOW_RAYS == 2 && (kWalk == WALK_LANE || kWalk == WALK_LANE_NS)) {
-        /* two records per thread (trace_any_lane2): entries e0 + t and e0 + t + blockDim.x */
-        for (uint32_t e0 = blockIdx.x / kQParts * 2u * blockDim.x; e0 < count; e0 += 2u * pstride) {
-            const uint32_t e_0 = e0 + threadIdx.x, e_1 = e_0 + blockDim.x;
-            const bool act0 = e_0 < count, act1 = e_1 < count;
-            float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), b0 = make_float4(0.f, 0.f, 1.f, 0.f), a1 = a0, b1 = b0;
-            if (act0) { a0 = B.nee[0][pbase + e_0]; b0 = B.nee[1][pbase + e_0]; }
-            if (act1) { a1 = B.nee[0][pbase + e_1]; b1 = B.nee[1][pbase + e_1]; }
-            bool occ0, occ1;
-            trace_any_lane2<kWalk == WALK_LANE_NS ? 0 : 1>(sc, nee_ray(a0, b0), act0, nee_ray(a1, b1), act1, occ0, occ1);
-            if (act0 && !occ0) visible(pbase + e_0, a0, b0);
-            if (act1 && !occ1) visible(pbase + e_1, a1, b1);
         }
         return;
     }
@@ -2241,11 +1980,6 @@ __global__ void __launch_bounds__(256, AMVPT_SHADOW_WAVES) k_shadow(KParams P, c
     }
 }
 
-/* waves per SIMD k_bounce's register allocation must allow: 5 (<= 96 VGPRs, from 101 at 4) hides
- * more of the state loads and the fused NEE walk (109.7 vs 118.3 ms per config-M frame, A/B r02z) */
-#ifndef AMVPT_BOUNCE_WAVES
-#define AMVPT_BOUNCE_WAVES 5
-#endif
 /* bounce_vertex's state hooks when the whole path state stays in registers (k_bounce) */
 struct NoPark {
     AD void in(PathState &, Pcg &) const {}
@@ -2406,32 +2140,6 @@ __global__ void __launch_bounds__(256, AMVPT_BOUNCE_WAVES) k_bounce(KParams P, c
  * are the same operations in the same order as the k_extend / k_bounce wavefronts.
  * The work counters (cnt_out of the queue pair) are zeroed by the host before the launch.
  */
-#ifndef AMVPT_BOX_LDS
-#define AMVPT_BOX_LDS 1   /* k_suffix_fused stages the box triangles in LDS for box_walk's per-lane loads (0: L1/L2, A/B) */
-#endif
-#ifndef AMVPT_FUSE_BVH
-/* 1: BVH scenes run k_suffix_fused too (per-lane / wave-uniform walks inside the fused loop).  Off:
- * on the 3.6 k-triangle mesh it measured 519 vs 608 Msamples/s for the wavefront suffix (r03m) --
- * the walks, latency-bound on dependent node loads, lose more at the fused kernel's register budget
- * (80 VGPRs + 144 B of spills) than the fused loop saves in state traffic and launches */
-#define AMVPT_FUSE_BVH 0
-#endif
-#ifndef AMVPT_FUSED_BLOCKS
-/* blocks per queue partition (x kQParts blocks of 256 threads), more than are resident at once:
- * blocks that start late find their partition partly drained, which evens out the tail
- * (config M, 2^23-lane chunks, suffix ms: 5 -> 163.7, 8 -> 149.0, 16 -> 144.8, 24..64 -> 144.8,
- * r02fb; 2^25-lane chunks: 12 -> 135.2, 16 -> 133.5, 24 -> 132.4, 32 -> 132.7, r02fm) */
-#define AMVPT_FUSED_BLOCKS 24
-#endif
-#ifndef AMVPT_FUSED_WAVES
-/* 6 waves/SIMD (80 VGPRs, 68 B of spills): suffix 146.4 -> 143.2 ms per config-M frame; 4 waves 157.8 (r02fc);
- * 5 waves (no spills) 1480 vs 1510 Msamples/s at 6 (r03m) */
-#define AMVPT_FUSED_WAVES 6
-#endif
-#ifndef AMVPT_FUSED_PARK
-/* path-state groups k_suffix_fused keeps in LDS between the phases that use them (LdsPark) */
-#define AMVPT_FUSED_PARK 0x2f
-#endif
 enum : int { PK_RES = 1, PK_PREV = 2, PK_THR = 4, PK_RNG = 8, PK_RAY = 16, PK_NEE = 32 };
 /* LDS slots (floats) of a parked path: field f of block thread t at base[f * 256 + t] */
 enum : int { PF_RES = 0, PF_IDX = 3, PF_PREVP = 4, PF_PREVPDF = 7, PF_THR = 8, PF_DEPTH = 11, PF_RNG = 12, PF_RESNEE = 16,
@@ -2494,12 +2202,6 @@ template <int kMask> struct LdsPark {
 template <int kMask> constexpr uint32_t park_lds_bytes() { return kMask ? park_fields(kMask) * 4u * kFusedBlock : 0u; }
 constexpr uint32_t kFusedParkBytes = park_lds_bytes<AMVPT_FUSED_PARK>();
 
-#ifndef AMVPT_FUSED_WAVES_GLOSSY
-/* the instance with microfacet BSDFs (kDiff = false): its own register budget.  5 waves/SIMD (96 VGPRs, no
- * scratch) and 6 (80 VGPRs, 44 B of scratch) run the C3 suffix in the same time (305.1 vs 303.9 ms, r04b);
- * at 6 its PMC bytes are 1.54x the algorithmic ones (r04d_traffic_C3.json), so 5 */
-#define AMVPT_FUSED_WAVES_GLOSSY 5
-#endif
 template <bool kTab, bool kDiff, int kW>
 __global__ void __launch_bounds__(kFusedBlock, kDiff ? AMVPT_FUSED_WAVES : AMVPT_FUSED_WAVES_GLOSSY)
     k_suffix_fused(KParams P, const DScene *Sp, Bufs B) {
@@ -2508,8 +2210,8 @@ __global__ void __launch_bounds__(kFusedBlock, kDiff ? AMVPT_FUSED_WAVES : AMVPT
     /* the parked state sits in front of the staged tables (dynamic LDS: [park][tables]) */
     const LdsPark<kPk> pk{(lds_float *) (uint32_t) (uintptr_t) lds + threadIdx.x};
     DScene S = *Sp;
-    SceneRef sc = stage_scene<kTab, false>(S, lds + kFusedParkBytes, P.trav_mode, nullptr, 0, P.box_screen != 0,
-                                           AMVPT_BOX_LDS != 0);
+    /* the box triangles are staged in LDS for box_walk's per-lane loads */
+    SceneRef sc = stage_scene<kTab, false>(S, lds + kFusedParkBytes, P.trav_mode, nullptr, 0, P.box_screen != 0, true);
     const uint32_t part = blockIdx.x % kQParts;
     const uint32_t count = B.cnt_in[part * kCntStride], pbase = part * B.qcap;
     uint32_t *const work = B.cnt_out + part * kCntStride;
@@ -2534,10 +2236,9 @@ __global__ void __launch_bounds__(kFusedBlock, kDiff ? AMVPT_FUSED_WAVES : AMVPT
             }
         }
         if (!wave_any(live)) break;
-        constexpr bool kBruteW = kW == WALK_BRUTE || kW == WALK_BRUTE_NS;
+        static_assert(kW == WALK_BRUTE || kW == WALK_BRUTE_NS, "the fused suffix runs the brute-force walks only");
         if (kPk & PK_RAY) s.ray = Ray{pk.get3(PF_RAY), pk.get3(PF_RAY + 3), kLargest};
-        Hit h{kInf, 0.f, 0.f, -1};
-        if (kBruteW || live) h = walk_closest<kW>(sc, s.ray);   /* brute force: every lane of the wave walks */
+        const Hit h = walk_closest<kW>(sc, s.ray);   /* brute force: every lane of the wave walks */
         bool keep = false, nee = false;
         Ray shr;
         f3 nee_to;
@@ -2548,9 +2249,7 @@ __global__ void __launch_bounds__(kFusedBlock, kDiff ? AMVPT_FUSED_WAVES : AMVPT
         /* wave-level counts in scalar registers (no per-lane 64-bit counters across the loop) */
         verts += (uint32_t) __popcll(__ballot(live));
         shadows += (uint32_t) __popcll(__ballot(nee));
-        bool occluded = true;
-        if constexpr (kBruteW) occluded = brute_any<kW == WALK_BRUTE>(sc, shr, !nee);
-        else if (nee) occluded = walk_any<kW>(sc, shr);
+        const bool occluded = brute_any<kW == WALK_BRUTE>(sc, shr, !nee);
         if (nee && !occluded) pk.set_res(s, pk.res_nee(res_nee));
         if (live && !keep) {
             const C3 r = pk.res(s);
@@ -2819,11 +2518,8 @@ __global__ void __launch_bounds__(256) k_prim_req(KParams P, const DScene *Sp, c
 /*
  * k_prim_hit + k_prim_req in one launch (wave-uniform BVHs, whose walk needs no LDS): the raygen
  * is computed once and the hit goes straight into the request code (it is still stored for
- * k_mv_primary).  AMVPT_FUSE_PRIM=0 keeps the two launches (A/B).
+ * k_mv_primary).
  */
-#ifndef AMVPT_PRIM_HIT_WAVES_DEFER
-#define AMVPT_PRIM_HIT_WAVES_DEFER 8   /* as AMVPT_VIS_WAVES_DEFER, for the primary closest-hit walk */
-#endif
 template <int G, bool kTab, bool kDiff, int kSph = 1>
 __global__ void __launch_bounds__(256, kSph == 2 ? AMVPT_PRIM_HIT_WAVES_DEFER : 1) k_prim_hit_req(KParams P, const DScene *Sp, const DView *V, Bufs B) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -2843,34 +2539,16 @@ __global__ void __launch_bounds__(256, kSph == 2 ? AMVPT_PRIM_HIT_WAVES_DEFER : 
 /* one block = 64 lanes x G slots, wave k traces slot k of the block's 64 lanes (G = 0: 16 waves,
  * wave w traces slots w, w + 16, ... of the runtime group size).  Wave-uniform walks with G > 0
  * (vis_pairs): one block = 128 lanes, wave k traces slot k of both 64-lane groups at once
- * (trace_any2_uni).  AMVPT_VIS_PAIRS = 0 turns that off (A/B). */
-#ifndef AMVPT_VIS_PAIRS
-#define AMVPT_VIS_PAIRS 1
-#endif
+ * (trace_any2_uni). */
 template <int G> constexpr int vis_waves() { return G > 0 ? G : 16; }
-template <int G, bool kUni> constexpr bool vis_pairs() { return AMVPT_VIS_PAIRS && kUni && G > 0; }
-#ifndef AMVPT_VIS_RAYS
-/* rays per lane of the pair walk (trace_any2_uni; > 2: trace_anyN_uni, A/B -- 4 rays: config-M k_vis 43.5 ->
- * 50.5 ms, C3 165 -> 238 ms, r04z_ab_*.log) */
-#define AMVPT_VIS_RAYS 2
-#endif
-/* waves per SIMD the paired walk's register allocation must allow (0: no bound).  Measured at
- * config M (r02ac): unbounded 96 VGPRs / 5 waves 69.3 ms, 6 waves (80 VGPRs, 12 B scratch)
- * 63.5 ms, 8 waves (64 VGPRs, 52 B scratch) 74.1 ms; one ray per lane, 8 waves: 72.3 ms */
-#ifndef AMVPT_VIS_WAVES
-#define AMVPT_VIS_WAVES 6
-#endif
+template <int G, bool kUni> constexpr bool vis_pairs() { return kUni && G > 0; }
+static_assert(AMVPT_VIS_RAYS == 2, "k_vis pairs its rays with trace_any2_uni: two per lane");
 template <int G, bool kUni> constexpr int vis_min_waves() { return vis_pairs<G, kUni>() ? AMVPT_VIS_WAVES : 0; }
-#ifndef AMVPT_VIS_WAVES_DEFER
-/* k_vis with deferred sphere tests: the walk needs what the sphere-free walk needs (41 VGPRs), so the register
- * budget is that of 8 waves/SIMD; the float64 tests after the walk -- rare, after the screen -- may spill */
-#define AMVPT_VIS_WAVES_DEFER 8
-#endif
 template <int G, bool kUni, int kSph = 1>
 __global__ void __launch_bounds__(64 * vis_waves<G>(), (kSph == 2 && vis_pairs<G, kUni>() ? AMVPT_VIS_WAVES_DEFER : vis_min_waves<G, kUni>())) k_vis(KParams P, const DScene *Sp, const DView *V, Bufs B) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     DScene S = *Sp;
-    SceneRef sc = stage_scene<false, true, (AMVPT_TREELETS & 4) != 0>(S, lds, P.trav_mode);
+    SceneRef sc = stage_scene<false>(S, lds, P.trav_mode);
     const int Gn = group_size<G>(P);
     if constexpr (vis_pairs<G, kUni>()) {
         /* kVR = AMVPT_VIS_RAYS rays per lane: 64-lane groups h of the block's 64 x kVR lanes, one view slot k per wave */
@@ -2895,8 +2573,7 @@ __global__ void __launch_bounds__(64 * vis_waves<G>(), (kSph == 2 && vis_pairs<G
             }
         }
         bool occ[kVR];
-        if constexpr (kVR == 2) trace_any2_uni<kSph>(sc, r[0], act[0], r[1], act[1], occ[0], occ[1]);
-        else trace_anyN_uni<kSph, kVR>(sc, r, act, occ);
+        trace_any2_uni<kSph>(sc, r[0], act[0], r[1], act[1], occ[0], occ[1]);
 #pragma unroll
         for (int h = 0; h < kVR; ++h) {
             const unsigned long long m = __ballot(occ[h]);
@@ -2939,7 +2616,7 @@ __global__ void __launch_bounds__(64 * vis_waves<G>(), (kSph == 2 && vis_pairs<G
 /* ------------------------------------------------------------------ */
 
 enum : uint32_t { VF_VALID = 1u, VF_INDIRECT = 2u };
-/* generic stage (AMVPT_WAVE_DIFF): the all-diffuse waves' compact records, one weight per view [G][n], after
+/* generic stage: the all-diffuse waves' compact records, one weight per view [G][n], after
  * the two float4 planes of the generic view records */
 AD float *vrec_compact(const Bufs &B, int Gn, uint32_t n) { return reinterpret_cast<float *>(B.vrec + (size_t) 2 * Gn * n); }
 enum : uint32_t { LF_VALIDRAY = 1u, LF_ADAPT = 2u, LF_REUSE = 4u, LF_MIS = 8u, LF_DIRECT = 16u,
@@ -2997,84 +2674,22 @@ AD f3 reflect_l(f3 w) { return mk(-w.x, -w.y, w.z); }
  * View records are written as soon as each part is final:
  *   rec0[k] = (splat x, splat y, weight, flags), rec1[k] = result, rec2[k] = bsdf_val.
  */
-#ifndef AMVPT_BOUNCE_TAB
-#define AMVPT_BOUNCE_TAB 1
-#endif
-#ifndef AMVPT_PRIM_TAB
-#define AMVPT_PRIM_TAB 1
-#endif
-#ifndef AMVPT_PRIM_SLOT_ORDER
-#define AMVPT_PRIM_SLOT_ORDER 1
-#endif
-#ifndef AMVPT_DEFER_SAMPLE
-/* camera_selection's per-view BSDF samples: the loop takes each view's sample type (no sampling)
- * and one bsdf_sample runs for the last replacing view (0: a sample per view, A/B) */
-#define AMVPT_DEFER_SAMPLE 1
-#endif
-#ifndef AMVPT_PAIR_REGS
-/* pair-sum operands of views j >= 1 in registers for G <= 8: k_mv_primary 459 -> 427 ms per C3 frame
- * (0: read from LDS per pair, A/B r03g); reading view k's own fields from the register copies too
- * (uniform dynamic index) measured slower, 444 ms (r03h) */
-#define AMVPT_PAIR_REGS 1
-#endif
-#ifndef AMVPT_PDF_REGS
-/* 1: with the pair registers, the views' F_PDF lives in registers only (written under a uniform view index in
- * camera_selection, read the same way in mis_weights), so the generic instance's per-view LDS state drops from 6
- * to 5 fields: 29.4 -> 25.3 KB per 128-thread block at C3, 6 blocks (12 waves, its VGPR limit) per CU instead of
- * 5 (0: A/B) */
-#define AMVPT_PDF_REGS 1
-#endif
-#ifndef AMVPT_DIFF_REGS
-/* 1: the all-diffuse body (kDiff: the all-diffuse scenes' k_mv_primary and the mixed scenes' all-diffuse waves) of
- * the compile-time groups up to 8 views keeps both per-view fields, F_PDF and F_JP, in registers (written and read
- * under a uniform view index, the MIS pair sums unrolled over register operands), so it has no per-view LDS state
- * and no LDS read per pair term.  Measured slower (r06ad: config-M k_mv_primary 40.0 -> 41.7 ms, C3 and mesh neutral --
- * the uniform-index select chains cost more issue than the LDS reads they replace), so 0: the two LDS fields */
-#define AMVPT_DIFF_REGS 0
-#endif
-/* the all-diffuse body keeps F_PDF and F_JP in registers (see AMVPT_DIFF_REGS) */
-template <int G, bool kDiff> __host__ __device__ constexpr bool diff_regs() {
-    return AMVPT_DIFF_REGS && AMVPT_PAIR_REGS && kDiff && G >= 2 && G <= 8;
-}
-/* the generic compile-time groups keep F_PDF out of LDS (see AMVPT_PDF_REGS) */
-template <int G, bool kDiff> __host__ __device__ constexpr bool pdf_in_regs() {
-    return (AMVPT_PAIR_REGS && AMVPT_PDF_REGS && !kDiff && G >= 2 && G <= 8) || diff_regs<G, kDiff>();
-}
+/* the generic compile-time groups up to 8 views hold the pair-sum operands of views j >= 1 in registers
+ * (k_mv_primary 459 -> 427 ms per C3 frame, r03g), and with them the views' F_PDF lives in registers only (written
+ * under a uniform view index in camera_selection, read the same way in mis_weights), so the generic instance's
+ * per-view LDS state drops from 6 to 5 fields: 29.4 -> 25.3 KB per 128-thread block at C3, 6 blocks (12 waves, its
+ * VGPR limit) per CU instead of 5 */
+template <int G, bool kDiff> __host__ __device__ constexpr bool pdf_in_regs() { return !kDiff && G >= 2 && G <= 8; }
 template <int G, bool kDiff> __host__ __device__ constexpr int vs_fields() {
-    return kDiff ? (diff_regs<G, kDiff>() ? 0 : kVsFieldsDiff) : VS_FIELDS - (pdf_in_regs<G, kDiff>() ? 1 : 0);
+    return kDiff ? kVsFieldsDiff : VS_FIELDS - (pdf_in_regs<G, kDiff>() ? 1 : 0);
 }
-#ifndef AMVPT_FUSED_TWO_STREAMS
-#define AMVPT_FUSED_TWO_STREAMS 0   /* 1: fused-suffix scenes alternate chunks over two streams too (A/B) */
-#endif
-#ifndef AMVPT_CHUNK_STREAMS
-#define AMVPT_CHUNK_STREAMS 4   /* chunk streams of a per-depth-suffix render (1: every chunk on the render stream; mesh
-                                 * 962-973 / 984-988 / 1001-1002 Msamples/s with 2 / 3 / 4, r05zi; A/B) */
-#endif
-#ifndef AMVPT_TILE_SLOTS
-/* 4 x 4 pixel tiles per row-splat block (see tile_slot_lane): config M 1472 -> 1521 Msamples/s (splat
- * 106.3 -> 100.7 ms, and the fused suffix 134 -> 129.6 ms: its queue drains spatially coherent paths);
+/* Row-splat blocks take 4 x 4 pixel tiles (KParams::tile_w, see tile_slot_lane): config M 1472 -> 1521 Msamples/s
+ * (splat 106.3 -> 100.7 ms, and the fused suffix 134 -> 129.6 ms: its queue drains spatially coherent paths);
  * with block-wide windows instead of wave windows it lost (splat 122 ms, r03s) */
-#define AMVPT_TILE_SLOTS 1
-#endif
-#ifndef AMVPT_PDF_ROW
-#define AMVPT_PDF_ROW 1   /* the pairwise MIS sum hoists wi_k's pdf row (0: per-pair bsdf_pdf, A/B) */
-#endif
-#ifndef AMVPT_COH_UNI
-/* 1: k_prim_hit(_req) and k_vis walk wave-uniformly (scalar node loads, the wave enters a node when
+/* k_prim_hit(_req) and k_vis walk wave-uniformly (scalar node loads, the wave enters a node when
  * any lane's ray hits its box) on BVHs of any size -- a wave's camera / visibility rays are nearly
  * identical (4 pixels x 16 samples, one target view per wave), and the primary walk fuses with the
- * request code (k_prim_hit_req).  3.6 k-triangle mesh: 629.9 -> 663.8 Msamples/s (r03v); 0: per-lane
- * walks above kUniformNodeLimit nodes (A/B) */
-#define AMVPT_COH_UNI 1
-#endif
-#ifndef AMVPT_WAVE_DIFF
-/* 1: the generic k_mv_primary runs the all-diffuse body for waves whose primary hits are all plain
- * diffuse (mixed-material scenes; A/B 0) */
-#define AMVPT_WAVE_DIFF 1
-#endif
-#ifndef AMVPT_PRIM_WAVES
-#define AMVPT_PRIM_WAVES 1
-#endif
+ * request code (k_prim_hit_req).  3.6 k-triangle mesh: 629.9 -> 663.8 Msamples/s (r03v) */
 /*
  * kDiff (every BSDF of the scene is plain `diffuse`): pdf_Mat is 1 and eval/pdf depend
  * on a direction only through the sign of its z, a view's BSDF sample is the primary's
@@ -3099,7 +2714,6 @@ AD void mv_primary_lane(const KParams &P, const DScene &S, const SceneRef &sc, c
     static_assert(!kFuse || (kDiff && !kGenRec && G >= 2), "the fused primary vertex: all-diffuse compile-time groups");
     const int Gn = group_size<G>(P);
     constexpr bool kPdfRegs = pdf_in_regs<G, kDiff>();
-    constexpr bool kJpRegs = diff_regs<G, kDiff>();   /* F_JP in registers as well: no per-view LDS state */
     /* field f of view slot k (kPdfRegs: F_PDF is not stored, the other fields move down one) */
 #define VSF(f, k) vs[(((f) - (kPdfRegs ? 1 : 0)) * Gn + (k)) * vs_stride]
     PathState ps;
@@ -3210,15 +2824,7 @@ AD void mv_primary_lane(const KParams &P, const DScene &S, const SceneRef &sc, c
                 Surf p0 = camera_sample_surface(V[view_of(0)], si, p_hit, apx, apy);
                 const float pdf0 = p0.pdf, Jp0 = p0.Jp, iJp0 = p_hit ? rcp(p0.Jp) : 0.f;
                 if (!kPdfRegs) VSF(F_PDF, 0) = pdf0;
-                /* kJpRegs: the views' F_JP (slot 0 and slots 1..G-1) */
-                float rJp[kJpRegs ? G : 1];
-                if constexpr (kJpRegs) {
-                    rJp[0] = Jp0;
-#pragma unroll
-                    for (int j = 1; j < G; ++j) rJp[j] = 0.f;
-                } else {
-                    VSF(F_JP, 0) = Jp0;
-                }
+                VSF(F_JP, 0) = Jp0;
                 mset(vmask, 0, p_hit);
                 mset(imask, 0, p_hit);
                 const f3 wo_r0 = reflect_l(si.wi);
@@ -3246,7 +2852,7 @@ AD void mv_primary_lane(const KParams &P, const DScene &S, const SceneRef &sc, c
                     for (int j = 0; j < G; ++j) rPdf[j] = 0.f;
                 }
                 float n_direct = 1.f, n_indir = 2.f;
-                int rep_k = 0;   /* AMVPT_DEFER_SAMPLE: the view whose BSDF sample replaces the primary's */
+                int rep_k = 0;   /* the view whose BSDF sample replaces the primary's */
                 (void) rep_k;
 #pragma unroll 1
                 for (int k = 1; k < Gn; ++k) {
@@ -3272,12 +2878,7 @@ AD void mv_primary_lane(const KParams &P, const DScene &S, const SceneRef &sc, c
                     float pdf_J = J > 1.f ? rcp(J) : J;
                     float pdf_Sel = pdf_Mat * pdf_J;
                     valid = valid && (rng.next_1d() < pdf_Sel);
-                    if constexpr (kJpRegs) {
-#pragma unroll
-                        for (int j = 1; j < G; ++j) rJp[j] = j == k ? r.Jp : rJp[j];
-                    } else {
-                        VSF(F_JP, k) = r.Jp;
-                    }
+                    VSF(F_JP, k) = r.Jp;
                     if constexpr (kPdfRegs) {
                         const float pk = valid ? r.pdf : 0.f;
 #pragma unroll
@@ -3289,23 +2890,15 @@ AD void mv_primary_lane(const KParams &P, const DScene &S, const SceneRef &sc, c
                     bool replace = n_indir * rng.next_1d() < 1.f;
                     C3 bvk;
                     float bpk;
-                    BSample bsk;
-                    C3 bwk;
                     bsdf_eval_pdf<kDiff>(S.bsdfs, b, CTX_ALL, wik, wo, valid, bvk, bpk);
                     direct = direct && bpk > 0.f;
                     direct_pdf += direct ? bpk : 0.f;
                     n_direct += (float) direct;
                     if (!kDiff) {
-#if AMVPT_DEFER_SAMPLE
-                        /* only the last replacing view's sampled direction survives the loop: its type
-                         * decides here, the one bsdf_sample runs after the loop */
+                        /* camera_selection's per-view BSDF samples: only the last replacing view's sampled direction
+                         * survives the loop, so its type decides here and the one bsdf_sample runs after the loop */
                         indirect = indirect && bsdf_sample_type(S.bsdfs, b, CTX_ALL, wik, valid) == bsmp.type;
                         if (indirect && replace) rep_k = k;
-#else
-                        bsdf_sample(S.bsdfs, b, CTX_ALL, wik, r2a, r2b, valid, bsk, bwk);
-                        indirect = indirect && bsk.type == bsmp.type;
-                        if (indirect && replace) bsmp.wo = bsk.wo;
-#endif
                     }
                     /* kDiff: a valid view's sample is the primary's (same type, same wo) */
                     (void) replace;
@@ -3313,14 +2906,12 @@ AD void mv_primary_lane(const KParams &P, const DScene &S, const SceneRef &sc, c
                     mset(vmask, k, valid);
                     mset(imask, k, indirect);
                 }
-#if AMVPT_DEFER_SAMPLE
                 if (!kDiff && rep_k > 0) {
                     BSample bsk;
                     C3 bwk;
                     bsdf_sample(S.bsdfs, b, CTX_ALL, wi_of(rep_k), r2a, r2b, true, bsk, bwk);
                     bsmp.wo = bsk.wo;
                 }
-#endif
                 direct_pdf /= n_direct;
                 const float mis_em = ds.delta ? 1.f : mis_weight(ds.pdf, direct_pdf);
                 const C3 emis_mis = em_w * mis_em;
@@ -3349,14 +2940,13 @@ AD void mv_primary_lane(const KParams &P, const DScene &S, const SceneRef &sc, c
                 float n_ind = 0.f, pdf = 0.f;
                 /* the pair sums' operands of views j >= 1 (same for every k): registers for the
                  * compile-time groups up to 8 views, LDS otherwise */
-                constexpr int kPR = (AMVPT_PAIR_REGS && (!kDiff || kJpRegs) && G >= 2 && G <= 8) ? G : 1;
+                constexpr int kPR = (!kDiff && G >= 2 && G <= 8) ? G : 1;
                 constexpr int kPW = kDiff ? 1 : kPR;   /* the all-diffuse body reads no wi_j */
                 float pJp[kPR], pPdf[kPR], pWx[kPW], pWy[kPW], pWz[kPW];
                 if constexpr (kPR > 1) {
 #pragma unroll
                     for (int j = 1; j < kPR; ++j) {
-                        if constexpr (kJpRegs) pJp[j] = rJp[j < G ? j : 0];
-                        else pJp[j] = VSF(F_JP, j);
+                        pJp[j] = VSF(F_JP, j);
                         if constexpr (kPdfRegs) pPdf[j] = rPdf[j < G ? j : 0];
                         else pPdf[j] = VSF(F_PDF, j);
                         if constexpr (!kDiff) { pWx[j] = VSF(F_WX, j); pWy[j] = VSF(F_WY, j); pWz[j] = VSF(F_WZ, j); }
@@ -3365,14 +2955,7 @@ AD void mv_primary_lane(const KParams &P, const DScene &S, const SceneRef &sc, c
 #pragma unroll 1
                 for (int k = 0; k < Gn; ++k) {
                     const bool vk = mget(vmask, k);
-                    float Jpk;
-                    if constexpr (kJpRegs) {
-                        Jpk = rJp[0];
-#pragma unroll
-                        for (int j = 1; j < G; ++j) Jpk = j == k ? rJp[j] : Jpk;
-                    } else {
-                        Jpk = VSF(F_JP, k);
-                    }
+                    const float Jpk = VSF(F_JP, k);
                     const float iJpk = k == 0 ? iJp0 : (vk ? rcp(Jpk) : 0.f);
                     const f3 wik = wi_of(k);
                     const float pdfMk = kDiff ? 1.f : VSF(F_PDFM, k);
@@ -3396,9 +2979,8 @@ AD void mv_primary_lane(const KParams &P, const DScene &S, const SceneRef &sc, c
                     bool cond = k > 0 ? vk : bd.reuse;
                     float acc = 0.f;
                     if (!kDiff && cond && !bd.diffuse) {
-#if AMVPT_PDF_ROW
+                        /* wi_k's pdf row, hoisted out of the pair sum */
                         const PdfRow row = pdf_row(S.bsdfs, b, CTX_GLOSSY, wik);
-#endif
                         if constexpr (kPR > 1) {
 #pragma unroll
                             for (int j = 1; j < kPR; ++j) {
@@ -3407,13 +2989,8 @@ AD void mv_primary_lane(const KParams &P, const DScene &S, const SceneRef &sc, c
                                 const int jw = kDiff ? 0 : j;   /* (the all-diffuse body never runs this branch) */
                                 const f3 worj = reflect_l(mk(pWx[jw], pWy[jw], pWz[jw]));
                                 const bool vj = mget(vmask, j);
-#if AMVPT_PDF_ROW
                                 const float pdf_Mat = P.fast_mis ? tv_pdf_fast(worj, wik, pdfMk, bd, vj)
                                                                  : tv_pdf_row(row, worj, pdfMk, bd, vj);
-#else
-                                const float pdf_Mat = P.fast_mis ? tv_pdf_fast(worj, wik, pdfMk, bd, vj)
-                                                                 : tv_pdf(S.bsdfs, worj, wik, pdfMk, bd, vj);
-#endif
                                 acc = fmadd(pPdf[j], pdf_J * pdf_Mat, acc);
                             }
                         } else
@@ -3423,13 +3000,8 @@ AD void mv_primary_lane(const KParams &P, const DScene &S, const SceneRef &sc, c
                             float pdf_J = vmin(sqr(VSF(F_JP, j) * iJpk), 1.f);
                             f3 worj = reflect_l(mk(VSF(F_WX, j), VSF(F_WY, j), VSF(F_WZ, j)));
                             const bool vj = mget(vmask, j);
-#if AMVPT_PDF_ROW
                             float pdf_Mat = P.fast_mis ? tv_pdf_fast(worj, wik, pdfMk, bd, vj)
                                                        : tv_pdf_row(row, worj, pdfMk, bd, vj);
-#else
-                            float pdf_Mat = P.fast_mis ? tv_pdf_fast(worj, wik, pdfMk, bd, vj)
-                                                       : tv_pdf(S.bsdfs, worj, wik, pdfMk, bd, vj);
-#endif
                             acc = fmadd(VSF(F_PDF, j), pdf_J * pdf_Mat, acc);
                         }
                     } else if constexpr (kPR > 1) {
@@ -3584,15 +3156,9 @@ AD bool wave_diffuse(const KParams &P, const DScene &S, const SceneRef &sc, cons
     }
     return !wave_any(!dl);
 }
-/* kDiff: the all-diffuse scenes' kernel.  Otherwise (AMVPT_WAVE_DIFF) two launches of the generic stage:
+/* kDiff: the all-diffuse scenes' kernel.  Otherwise two launches of the generic stage:
  * kDW = true runs the waves whose primary hits are all diffuse with the all-diffuse body at its own
  * register budget (generic records), kDW = false the others with the generic body */
-#ifndef AMVPT_PRIM_FUSE_WAVES
-/* waves per SIMD the fused primary vertex's register allocation must allow (kFuse).  Measured at config M, G = 8
- * (r07a_ab_fused_primary.log): unbounded / 5 waves 87 VGPRs, no scratch, k_mv_primary 74.0 ms per frame; 4 waves
- * the same; 6 waves (80 VGPRs, 24 B scratch) 71.6 ms; 7 waves (72 VGPRs, 56 B) 73.9 ms; 8 waves 78.2 ms */
-#define AMVPT_PRIM_FUSE_WAVES 6
-#endif
 /* kFuse: the whole primary vertex in this launch (mv_primary_lane: closest hit, shadow and visibility rays traced
  * in the lane); no k_prim_hit_req, no k_vis */
 template <int G, bool kTab, bool kDiff, bool kDW = false, bool kFuse = false>
@@ -3608,48 +3174,28 @@ __global__ void __launch_bounds__(prim_block<G>(), kFuse ? AMVPT_PRIM_FUSE_WAVES
     const uint32_t vs_stride = vs_glob ? P.vs_stride : (uint32_t) kPB;
     float *const vs = vs_glob ? B.vstate + (blockIdx.x * blockDim.x + threadIdx.x)
                               : reinterpret_cast<float *>(lds + vs_off) + threadIdx.x;
-#if AMVPT_PRIM_SLOT_ORDER
     /* threads run in slot order (a wave = 64 pixels of one sample, see slot_lane), so every
      * record store of a wave is 64 contiguous slots; the hit and the ballots are read at the
      * lane (16-B loads 256 B apart) */
     const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
     bool ok = slot < P.chunk_n;
     const uint32_t i = ok ? slot_lane(P, slot) : 0u;
-#else
-    /* threads run in lane order (a wave = 4 pixels x 16 samples); records go to the
-     * lane's slot (see slot_lane) */
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    bool ok = i < P.chunk_n;
-    const uint32_t slot = ok ? lane_slot(P, i) : 0u;
-#endif
     if constexpr (kDiff) {
         mv_primary_lane<G, kTab, true, false, kFuse>(P, S, sc, V, B, vs, vs_stride, slot, i, ok);
     } else if (kDW) {
         /* the waves whose primary hits are all plain diffuse (or misses): the all-diffuse body */
         if (wave_diffuse(P, S, sc, B, i, ok)) mv_primary_lane<G, kTab, true, true>(P, S, sc, V, B, vs, vs_stride, slot, i, ok);
     } else {
-        /* the other waves (all of them without AMVPT_WAVE_DIFF) */
-        if (!(AMVPT_WAVE_DIFF && wave_diffuse(P, S, sc, B, i, ok)))
+        /* the other waves */
+        if (!wave_diffuse(P, S, sc, B, i, ok))
             mv_primary_lane<G, kTab, false, false>(P, S, sc, V, B, vs, vs_stride, slot, i, ok);
     }
 }
-
 
 /* ------------------------------------------------------------------ */
 /* k_splat_multi<G>: indirect accumulation + splats (mvpath_multi.h:343-368,44-76) */
 /* ------------------------------------------------------------------ */
 
-/* waves per SIMD the register allocation must allow: the 30-KB window admits 5 blocks (20 waves)
- * per CU, and 5 (<= 96 VGPRs) no longer spills (113.8 vs 117.9 ms per config-M frame, A/B r02z) */
-#ifndef AMVPT_SPLAT_SKIP
-#define AMVPT_SPLAT_SKIP 1   /* skip views without a valid splat in the wave (0: off, A/B) */
-#endif
-#ifndef AMVPT_SPLAT_BVW
-#define AMVPT_SPLAT_BVW 1   /* all-diffuse waves form Bv * pdfW inside the view loop (0: hoisted by the compiler, A/B) */
-#endif
-#ifndef AMVPT_SPLAT_WAVES
-#define AMVPT_SPLAT_WAVES 5
-#endif
 /* kRow: the row-reduced splat with wave windows (P.row_splat, RGBW), else the block window;
  * kWin = false (kRow only): the film is the whole quilt */
 /* kRec = false: an instance without the record and debug paths (the bench's and every plain render's
@@ -3714,9 +3260,9 @@ __global__ void __launch_bounds__(kSplatBlock, AMVPT_SPLAT_WAVES) k_splat_multi(
         if (P.needs_ap) { apx = rng.next_1d(); apy = rng.next_1d(); }
         p_idx = sensor_index(P, fmadd(sx, P.inv_w, P.adj_ox), fmadd(sy, P.inv_h, P.adj_oy));
     }
-    /* an all-diffuse wave of a mixed scene's generic stage (AMVPT_WAVE_DIFF) carries the compact
+    /* an all-diffuse wave of a mixed scene's generic stage carries the compact
      * records (vrec_compact): the all-diffuse reads below, at run time */
-    const bool kd = kDiff || (AMVPT_WAVE_DIFF && !wave_any(ok && !(lflags & LF_DIFFW)) && wave_any(ok));
+    const bool kd = kDiff || (!wave_any(ok && !(lflags & LF_DIFFW)) && wave_any(ok));
     const float *const vw = kDiff ? reinterpret_cast<const float *>(B.vrec) : vrec_compact(B, Gn, n);
     const float4 *const vR = B.vrec, *const vB = B.vrec + (size_t) Gn * n;
     uint32_t splats = 0, fallback = 0, nonfinite = 0, negative = 0;   /* per lane, <= G each */
@@ -3725,7 +3271,7 @@ __global__ void __launch_bounds__(kSplatBlock, AMVPT_SPLAT_WAVES) k_splat_multi(
     for (int k = 0; k < Gn; ++k) {
         /* a view no lane of the wave splats into: no reprojection, no put (the lane record carries the
          * valid bits of every view, both record formats; records / debug mode write every view's entry) */
-        if (AMVPT_SPLAT_SKIP && k > 0 && !rec_ && !dbg_) {
+        if (k > 0 && !rec_ && !dbg_) {
             /* wave windows skip per wave; the block window's put has block barriers, so its skip must be
              * block-uniform (a wave skipping alone would pair its next barriers with the wrong view's) */
             const bool any = kRow ? wave_any(ok && mget(vmask, k)) : __syncthreads_or(ok && mget(vmask, k));
@@ -3763,16 +3309,12 @@ __global__ void __launch_bounds__(kSplatBlock, AMVPT_SPLAT_WAVES) k_splat_multi(
                     const C3 Dn = {(lf & 0x100u) ? qnan : 0.f, (lf & 0x200u) ? qnan : 0.f, (lf & 0x400u) ? qnan : 0.f};
                     result = k == 0 ? R0 : csel(direct && valid, csel(mget(smask, k), Dp, Dn), c3(0.f));
                     if (mget(imask, k)) {
-#if AMVPT_SPLAT_BVW
                         /* Bv * pdfW formed here, per view: hoisted out of the view loop, the generic instance kept the
                          * three products in registers it did not have and spilled two of them (a scratch reload and
                          * wait per indirect view of every all-diffuse wave) */
                         float pw = pdfW;
                         asm volatile("" : "+v"(pw));
                         result = cfma(Bv * pw, indirect, result);
-#else
-                        result = cfma(Bv * pdfW, indirect, result);
-#endif
                     }
                 } else {
                     result = res0;
@@ -3859,38 +3401,8 @@ void launch_shadow(int walk, bool bin, dim3 grid, size_t lds, hipStream_t st, co
 ;
 #endif
 
-/* A/B knobs: kernel-path choices fixed in release builds.  A build with -DAMVPT_AB_KNOBS (tools/ab.sh
- * variant libraries) reads them once from the environment; results are identical in every setting.
- * Per-call path selection for tests goes through amvpt_render_opts.flags instead. */
-struct AbKnobs {
-    bool fuse_prim = true, fuse_vertex = true, row_splat = true, brute = true, fuse_nee = true, fuse_suffix = true;
-    uint32_t win_rs = AMVPT_WIN_RS, fused_blocks = AMVPT_FUSED_BLOCKS;
-};
-inline const AbKnobs &ab_knobs() {
-    static const AbKnobs k = [] {
-        AbKnobs r;
-#ifdef AMVPT_AB_KNOBS
-        auto off = [](const char *n) { const char *e = std::getenv(n); return e && e[0] == '0'; };
-        r.fuse_prim = !off("AMVPT_FUSE_PRIM");
-        r.fuse_vertex = !off("AMVPT_FUSE_VERTEX");
-        r.row_splat = !off("AMVPT_ROW_SPLAT");
-        r.brute = !off("AMVPT_BRUTE");
-        r.fuse_nee = !off("AMVPT_FUSE_NEE");
-        r.fuse_suffix = !off("AMVPT_FUSE_SUFFIX");
-        if (const char *e = std::getenv("AMVPT_WIN_RS")) r.win_rs = (uint32_t) std::strtoul(e, nullptr, 0) % 32u;
-        if (const char *e = std::getenv("AMVPT_FUSED_BLOCKS"))
-            r.fused_blocks = std::max<uint32_t>(1, std::min<uint32_t>(64, (uint32_t) std::strtoul(e, nullptr, 0)));
-#endif
-        return r;
-    }();
-    return k;
-}
-
 /* Per-kernel HIP-event timing of an instrumented render (amvpt_counters given): an
  * event pair around every launch on the render stream, resolved in batches. */
-#ifndef AMVPT_FLUSH_MARKS
-#define AMVPT_FLUSH_MARKS 1
-#endif
 struct KTimer {
     static constexpr size_t kPairs = 128;
     bool on = false;
@@ -3931,10 +3443,10 @@ struct KTimer {
     }
     /* stage markers when not timing: a timing-enabled event record after each stage
      * (measured: a frame without them, or with hipEventDisableTiming markers, ran ~2 %
-     * slower; AMVPT_FLUSH_MARKS A/B) */
+     * slower) */
     hipEvent_t mark_ev = nullptr;
     void mark(hipStream_t st) {
-        if (on || !AMVPT_FLUSH_MARKS) return;
+        if (on) return;
         if (!mark_ev && hipEventCreate(&mark_ev) != hipSuccess) return;
         (void) hipEventRecord(mark_ev, st);
     }
@@ -3974,14 +3486,14 @@ void launch_primary(uint32_t cn, size_t lds_tab, size_t lds_bvh, hipStream_t st,
         /* sphere-free all-diffuse scenes walked wave-uniformly, compile-time groups: the whole vertex in one launch
          * (k_mv_primary's kFuse instance) -- the request code evaluated the functions k_mv_primary evaluates again,
          * only to hand k_vis its rays.  AMVPT_OPT_SPLIT_PRIMARY keeps the three launches. */
-        if (uni && ab_knobs().fuse_prim && ab_knobs().fuse_vertex && !P.split_prim && tab && diff && P.sph == 0) {
+        if (uni && !P.split_prim && tab && diff && P.sph == 0) {
             T.begin(AMVPT_K_MV_PRIMARY, st);
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mv_primary<G, true, true, false, true>), gp, dim3(kPB), lds_tab + lds_view, st, P, S, V, B);
             T.end(st);
             return;
         }
     }
-    if (uni && ab_knobs().fuse_prim) {
+    if (uni) {
         T.begin(AMVPT_K_PRIM_HIT, st);
         /* sphere-free scenes: the instances without float64 sphere code (the Cornell and mesh benches); scenes of
          * <= 64 spheres: the deferred sphere tests (P.sph, dgeom.h) */
@@ -4017,12 +3529,10 @@ void launch_primary(uint32_t cn, size_t lds_tab, size_t lds_bvh, hipStream_t st,
     if (tab && diff) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mv_primary<G, true, true>), gp, dim3(kPB), lds_tab + lds_view, st, P, S, V, B);
     else if (diff) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mv_primary<G, false, true>), gp, dim3(kPB), lds_tab + lds_view, st, P, S, V, B);
     else {
-        if (AMVPT_WAVE_DIFF) {
-            /* the all-diffuse waves first, with the all-diffuse body's smaller per-view LDS state */
-            const size_t lds_dw = B.vstate ? 0u : (size_t) vs_fields<G, true>() * group_size_host<G>(P) * kPB * sizeof(float);
-            if (tab) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mv_primary<G, true, false, true>), gp, dim3(kPB), lds_tab + lds_dw, st, P, S, V, B);
-            else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mv_primary<G, false, false, true>), gp, dim3(kPB), lds_tab + lds_dw, st, P, S, V, B);
-        }
+        /* the all-diffuse waves first, with the all-diffuse body's smaller per-view LDS state */
+        const size_t lds_dw = B.vstate ? 0u : (size_t) vs_fields<G, true>() * group_size_host<G>(P) * kPB * sizeof(float);
+        if (tab) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mv_primary<G, true, false, true>), gp, dim3(kPB), lds_tab + lds_dw, st, P, S, V, B);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mv_primary<G, false, false, true>), gp, dim3(kPB), lds_tab + lds_dw, st, P, S, V, B);
         if (tab) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mv_primary<G, true, false>), gp, dim3(kPB), lds_tab + lds_view, st, P, S, V, B);
         else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mv_primary<G, false, false>), gp, dim3(kPB), lds_tab + lds_view, st, P, S, V, B);
     }
@@ -4030,7 +3540,7 @@ void launch_primary(uint32_t cn, size_t lds_tab, size_t lds_bvh, hipStream_t st,
 }
 template <int G>
 void launch_splat(dim3 grid, hipStream_t st, const KParams &P, const DView *V, const Bufs &B, bool diff) {
-    const bool row = AMVPT_WAVE_WIN && P.row_splat && P.C == 4 && !P.film_fx;   /* deterministic: direct puts */
+    const bool row = P.row_splat && P.C == 4 && !P.film_fx;   /* deterministic: direct puts */
     const bool whole = P.fx0 == 0u && P.fy0 == 0u && P.fw == P.W && P.fh == P.H;
     if (P.filt_kind > FILT_GAUSSIAN) {
         /* tent, Mitchell, Catmull-Rom, Lanczos: the row splat of a plain render (render_impl sets row_splat for the
@@ -4255,7 +3765,6 @@ static amvpt_status arena_reserve(DevArena &A, void *&buf, size_t &have, size_t 
     return AMVPT_OK;
 }
 
-
 static void launch_suffix_fused(bool tab, bool diff, int walk, dim3 grid, size_t lds, hipStream_t st, const KParams &P,
                                 const DScene *S, const Bufs &B) {
 #define AMVPT_FUSED(T_, D_)                                                                                           \
@@ -4264,10 +3773,6 @@ static void launch_suffix_fused(bool tab, bool diff, int walk, dim3 grid, size_t
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_suffix_fused<T_, D_, WALK_BRUTE_NS>), grid, dim3(256), lds, st, P, S, B); \
         else if (walk == WALK_BRUTE)                                                                                  \
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_suffix_fused<T_, D_, WALK_BRUTE>), grid, dim3(256), lds, st, P, S, B); \
-        else if (AMVPT_FUSE_BVH && walk == WALK_UNI)                                                                  \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_suffix_fused<T_, D_, WALK_UNI>), grid, dim3(256), lds, st, P, S, B); \
-        else if (AMVPT_FUSE_BVH)                                                                                      \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_suffix_fused<T_, D_, WALK_LANE>), grid, dim3(256), lds, st, P, S, B); \
     } while (0)
     if (tab && diff) AMVPT_FUSED(true, true);
     else if (tab) AMVPT_FUSED(true, false);
@@ -4292,7 +3797,6 @@ static void launch_bounce(bool tab, bool diff, int nee_walk, dim3 grid, size_t l
 #undef AMVPT_BOUNCE_N
 #undef AMVPT_BOUNCE
 }
-
 
 typedef void (*primary_fn)(uint32_t, size_t, size_t, hipStream_t, const KParams &, const DScene *, const DView *,
                            const Bufs &, bool, bool, bool, KTimer &);
@@ -4428,7 +3932,6 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
     RoctxScope range_render("amvpt_render");
     const amvpt_params &Pp = *params;
     hipStream_t st = (hipStream_t) stream;
-    const AbKnobs &K = ab_knobs();
     const bool diffuse_spec = !(opts.flags & AMVPT_OPT_GENERIC_KERNELS);
     const uint32_t trav = opts.traversal;
     if (trav > 2) { set_error("amvpt_render: traversal must be 0 (auto), 1 (wave-uniform) or 2 (per-lane)"); return AMVPT_ERR_INVALID; }
@@ -4571,8 +4074,8 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
         P.bin_lo[a] = scene->root_lo[a];
         P.bin_scale[a] = ext > 0.f ? (float) (1u << kBinCellBits) / ext : 0.f;
     }
-    P.sph = !scene->has_spheres ? 0u : (AMVPT_SPHERE_DEFER && scene->n_sph <= 64u) ? 2u : 1u;
-    P.win_rs = K.win_rs;
+    P.sph = !scene->has_spheres ? 0u : scene->n_sph <= 64u ? 2u : 1u;
+    P.win_rs = AMVPT_WIN_RS;
     P.range_begin = rect ? 0 : lane_begin;
     P.rect = rect ? 1u : 0u;
     P.rect_x0 = rx0; P.rect_y0 = ry0;
@@ -4592,21 +4095,21 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
      * filter whose scalars are literals in the row kernels (default_filter, filter_eval_lit; checked bit for bit by
      * filter_setup): the default Gaussian in every render, tent of radius 1, Mitchell at B = C = 1/3 and Catmull-Rom
      * in plain multi-view renders (whole-quilt film, no records, no debug: the instances launch_splat has for them).
-     * AMVPT_OPT_BLOCK_SPLAT (or AMVPT_ROW_SPLAT=0 of an A/B build) keeps the per-lane block window */
+     * AMVPT_OPT_BLOCK_SPLAT keeps the per-lane block window */
     {
         bool literal = false;
         filter_setup(Pp, P.filt, P.filt_kind, &literal);
         const bool has_row = P.filt_kind == FILT_GAUSSIAN ||
                              ((P.filt_kind == FILT_TENT || P.filt_kind == FILT_MITCHELL || P.filt_kind == FILT_CATMULLROM) &&
                               G > 1 && whole_film && !records && !Pp.debug && !deterministic);
-        P.row_splat = (K.row_splat && !(opts.flags & AMVPT_OPT_BLOCK_SPLAT) && P.C == 4 && literal && has_row && P.pow2 &&
+        P.row_splat = (!(opts.flags & AMVPT_OPT_BLOCK_SPLAT) && P.C == 4 && literal && has_row && P.pow2 &&
                        spp_pp >= 16) ? 1u : 0u;
     }
     /* tiled slots: whole 4-row bands of a quilt row width divisible by 4, 16 samples per pixel and pass,
      * contiguous lane sets whose chunks start and end on band boundaries */
     {
         const uint64_t band = 4ull * QW * 16ull;
-        P.tile_w = (AMVPT_TILE_SLOTS && P.row_splat && spp_pp == 16 && QW % 4 == 0 && !rect && lane_begin % band == 0 &&
+        P.tile_w = (P.row_splat && spp_pp == 16 && QW % 4 == 0 && !rect && lane_begin % band == 0 &&
                     span % band == 0 && span <= 0xffffffffull) ? QW : 0u;
     }
 
@@ -4635,11 +4138,11 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
     const bool diff_rec = scene->all_diffuse && diffuse_spec && !wide;   /* kDiff instances, compact view records */
     /* the runtime instance's per-view state: LDS (64-thread blocks) while it fits, else a global
      * VS_FIELDS x G float plane per lane */
-    const size_t lds_tab_views = (AMVPT_PRIM_TAB && tables_staged(scene->dev, Pp.n_views))
+    const size_t lds_tab_views = tables_staged(scene->dev, Pp.n_views)
                                      ? scene->dev.tab_bytes + views_lds_bytes(Pp.n_views) : 0u;
     const bool vs_global = wide && lds_tab_views + (size_t) VS_FIELDS * G * 64 * sizeof(float) > 65536;
     const size_t per_lane = 2 * kQPlanes * 16 + 32 + 52 + 48 + 64 + 32 + 8 + 6 /* binned rays, binned NEE results, keys */ +
-                            (size_t) (diff_rec ? 4 : (AMVPT_WAVE_DIFF ? 36 : 32)) * G + (G + 7) / 8 +
+                            (size_t) (diff_rec ? 4 : 36) * G + (G + 7) / 8 +
                             (wide ? (size_t) 4 * 16 * mplanes : 0) + (vs_global ? (size_t) VS_FIELDS * 4 * G : 0);
     uint64_t chunk_max = opts.chunk_lanes ? std::max<uint64_t>(256, opts.chunk_lanes) : 0;
     if (chunk_max == 0) {
@@ -4651,22 +4154,20 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
     /* one partition holds the pushes of every kQParts-th producer block (<= 256 lanes each) */
     auto qcap_of = [](uint64_t c) { return (uint32_t) (((c + kQParts - 1) / kQParts + 512 + 63) & ~(uint64_t) 63); };
     const size_t stats_bytes = (size_t) kStats * kStatShards * 8, cnt_bytes = (size_t) 3 * kQParts * kCntStride * 4;
-    const bool tab_b = AMVPT_BOUNCE_TAB && tables_staged(scene->dev, 0), tab_p = AMVPT_PRIM_TAB && tables_staged(scene->dev, Pp.n_views);
+    const bool tab_b = tables_staged(scene->dev, 0), tab_p = tables_staged(scene->dev, Pp.n_views);
     const bool uni = scene_uniform(scene->dev.n_nodes, trav);
     /* the coherent primary and visibility rays walk wave-uniformly on every BVH in automatic mode
-     * (AMVPT_COH_UNI, see launch_primary); the incoherent suffix rays keep the per-lane walk */
-    const bool uni_coh = uni || (AMVPT_COH_UNI && trav == 0u);
+     * (see launch_primary); the incoherent suffix rays keep the per-lane walk */
+    const bool uni_coh = uni || trav == 0u;
     /* suffix walk: brute force for tiny scenes in auto mode */
-    int walk = uni ? WALK_UNI : (scene->has_spheres || !AMVPT_LANE_NS) ? WALK_LANE
-                              : (scene->bvh_tri_only && AMVPT_LANE_TRI) ? WALK_LANE_TRI : WALK_LANE_NS;
-    if (uni && trav == 0u && K.brute && scene->dev.n_prims <= kBrutePrims) walk = scene->has_spheres ? WALK_BRUTE : WALK_BRUTE_NS;
+    int walk = uni ? WALK_UNI : scene->has_spheres ? WALK_LANE : scene->bvh_tri_only ? WALK_LANE_TRI : WALK_LANE_NS;
+    if (uni && trav == 0u && scene->dev.n_prims <= kBrutePrims) walk = scene->has_spheres ? WALK_BRUTE : WALK_BRUTE_NS;
     const bool diff = diff_rec;                                                                           /* kDiff instances */
     /* NEE traced inside k_bounce (brute-force walks; AMVPT_OPT_SPLIT_NEE keeps k_shadow) */
-    const bool fuse_nee = (walk == WALK_BRUTE || walk == WALK_BRUTE_NS) && K.fuse_nee && !(opts.flags & AMVPT_OPT_SPLIT_NEE);
+    const bool fuse_nee = (walk == WALK_BRUTE || walk == WALK_BRUTE_NS) && !(opts.flags & AMVPT_OPT_SPLIT_NEE);
     /* the whole suffix in one launch, paths in registers (brute-force walks with fused NEE;
      * AMVPT_OPT_WAVEFRONT_SUFFIX keeps the per-depth k_extend / k_bounce wavefronts) */
-    const bool fuse_suffix = (fuse_nee || (AMVPT_FUSE_BVH && K.fuse_nee && !(opts.flags & AMVPT_OPT_SPLIT_NEE))) &&
-                             K.fuse_suffix && !(opts.flags & AMVPT_OPT_WAVEFRONT_SUFFIX);
+    const bool fuse_suffix = fuse_nee && !(opts.flags & AMVPT_OPT_WAVEFRONT_SUFFIX);
     /* chunks of the per-depth wavefront suffix (BVH scenes) take turns over up to four buffer sets on as many
      * streams (the render stream and the arena's side streams): one chunk's short deep-bounce launches and
      * tails leave CUs idle that the other chunks' kernels fill (mesh 550 -> 599 Msamples/s with two, round 2;
@@ -4675,15 +4176,15 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
      * times are not overlapped (AMVPT_OPT_ONE_STREAM forces one stream everywhere) */
     /* ray binning (k_bin_sort) for the per-lane suffix walks of BVHs read from device memory */
     const bool lane_walk = (walk == WALK_LANE || walk == WALK_LANE_NS || walk == WALK_LANE_TRI) && !fuse_suffix && scene_lds_bytes(scene->dev, trav) == 0u;
-    const bool bin_ext = lane_walk && (AMVPT_BIN & 1) && !(opts.flags & AMVPT_OPT_NO_BINNING);
-    const bool bin_nee = lane_walk && (AMVPT_BIN & 2) && !fuse_nee && !(opts.flags & AMVPT_OPT_NO_BINNING);
+    const bool bin_ext = lane_walk && !(opts.flags & AMVPT_OPT_NO_BINNING);   /* the extension rays (k_extend) */
+    const bool bin_nee = bin_ext && !fuse_nee;                                 /* the NEE rays (k_shadow) */
     auto set_bytes_of = [&](uint64_t c) {
         return cnt_bytes + per_lane * std::max<uint64_t>(c, (uint64_t) qcap_of(c) * kQParts) + 8192;
     };
     /* as many buffer sets as chunk streams, at most one per chunk of the render (chunk i on set i mod n across
      * the passes) and 192 GB of sets in all */
     auto sets_for = [&](uint64_t c) {
-        int n = (AMVPT_CHUNK_STREAMS > 1 && span > c && (!fuse_suffix || AMVPT_FUSED_TWO_STREAMS) &&
+        int n = (AMVPT_CHUNK_STREAMS > 1 && span > c && !fuse_suffix &&
                  !(opts.flags & AMVPT_OPT_ONE_STREAM)) ? std::min(AMVPT_CHUNK_STREAMS, kMaxChunkStreams) : 1;
         n = (int) std::min<uint64_t>((uint64_t) n, (uint64_t) n_passes * ((span + c - 1) / c));
         while (n > 2 && set_bytes_of(c) * (size_t) n > (192ull << 30)) --n;
@@ -4759,9 +4260,6 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
         (void) hipGetLastError();
     }
     if (P.tile_w && chunk % (4ull * QW * 16ull) != 0) P.tile_w = 0;   /* chunks must hold whole tile bands */
-    P.rcp_tpr = host_rcp(P.tile_w >> 2);   /* udiv_r's reciprocals of the final divisors */
-    P.rcp_run_len = host_rcp(P.run_len);
-    P.rcp_n_adapt = host_rcp(P.n_adapt);
     P.vs_stride = (uint32_t) chunk;
     const uint32_t qcap = qcap_of(chunk);
     const uint64_t qlen = (uint64_t) qcap * kQParts;
@@ -4859,11 +4357,11 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
         B.occ = (unsigned long long *) carve((size_t) 8 * G * ((chunk + 63) / 64));
         B.cnt_nee = cs.cntN;
         B.qcap = qcap;
-        B.vrec = (float4 *) carve((size_t) (diff_rec ? 4 : (AMVPT_WAVE_DIFF ? 36 : 32)) * G * chunk);
+        B.vrec = (float4 *) carve((size_t) (diff_rec ? 4 : 36) * G * chunk);
         cs.ka = cs.kb = nullptr;
         B.key_out = B.key_in = B.key_nee = nullptr;
         if (bin_ext || bin_nee) { B.sray[0] = (float4 *) carve(32 * qlen); B.sray[1] = nullptr; }
-        B.sgb = (bin_nee && AMVPT_NEE_CARRY) ? (float2 *) carve(8 * qlen) : nullptr;
+        B.sgb = bin_nee ? (float2 *) carve(8 * qlen) : nullptr;
         if (bin_ext) { cs.ka = (uint16_t *) carve(2 * qlen); cs.kb = (uint16_t *) carve(2 * qlen); }
         if (bin_nee) B.key_nee = (uint16_t *) carve(2 * qlen);
         if (wide) {
@@ -4880,22 +4378,19 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
     }
 
     const DScene *dS = (const DScene *) scene->dev_scene_struct;
-    const uint32_t fused_blocks = K.fused_blocks;
+    const uint32_t fused_blocks = AMVPT_FUSED_BLOCKS;
     const size_t lds = tab_b ? scene->dev.tab_bytes : 0u;                                           /* k_bounce */
-    /* k_suffix_fused: the box triangles staged for box_walk (AMVPT_BOX_LDS) */
-    const size_t box_lds = (AMVPT_BOX_LDS && P.box_screen) ? (size_t) scene->n_boxes * 12u * sizeof(DPrim) : 0u;
-    const size_t lds_ext = scene_lds_bytes(scene->dev, trav);                                       /* BVH walks */
-    const size_t lds_any0 = lds_ext + ((AMVPT_TREELETS & 1) ? tree_lds_bytes(scene->dev, trav) : 0u);    /* k_shadow: + any-hit treelet */
-    const size_t lds_vis = lds_ext + ((AMVPT_TREELETS & 4) ? tree_lds_bytes(scene->dev, trav) : 0u);     /* k_vis */
-    const size_t lds_close0 = lds_ext + ((AMVPT_TREELETS & 2) ? oct_tree_lds_bytes(scene->dev, trav) : 0u); /* k_extend: + octant treelets */
+    /* k_suffix_fused: the box triangles staged for box_walk */
+    const size_t box_lds = P.box_screen ? (size_t) scene->n_boxes * 12u * sizeof(DPrim) : 0u;
+    const size_t lds_ext = scene_lds_bytes(scene->dev, trav);                                       /* BVH walks: k_extend, k_shadow, k_vis */
     /* the two-box BVH walks (DScene::nodes2) for the per-lane suffix walks of BVHs read from device memory: a stack
      * of kStack2 u32 entries per thread after the kernels' other LDS (AMVPT_OPT_THREADED_BVH keeps the threaded walks) */
-    P.bvh2 = (scene->n_nodes2 && lane_walk && !(AMVPT_TREELETS & 3) && !(opts.flags & AMVPT_OPT_THREADED_BVH)) ? 1u : 0u;
+    P.bvh2 = (scene->n_nodes2 && lane_walk && !(opts.flags & AMVPT_OPT_THREADED_BVH)) ? 1u : 0u;
     const size_t stk_bytes = P.bvh2 ? (size_t) kStack2 * kStk2Stride * 4u : 0u;
-    P.stk_off_ext = (uint32_t) ((lds_close0 + 15u) & ~(size_t) 15u);
-    P.stk_off_any = (uint32_t) ((lds_any0 + 15u) & ~(size_t) 15u);
-    const size_t lds_close = P.bvh2 ? P.stk_off_ext + stk_bytes : lds_close0;
-    const size_t lds_any = P.bvh2 ? P.stk_off_any + stk_bytes : lds_any0;
+    P.stk_off_ext = (uint32_t) ((lds_ext + 15u) & ~(size_t) 15u);
+    P.stk_off_any = (uint32_t) ((lds_ext + 15u) & ~(size_t) 15u);
+    const size_t lds_close = P.bvh2 ? P.stk_off_ext + stk_bytes : lds_ext;
+    const size_t lds_any = P.bvh2 ? P.stk_off_any + stk_bytes : lds_ext;
     const size_t lds_prim = tab_p ? scene->dev.tab_bytes + views_lds_bytes(Pp.n_views) : 0u;        /* primary shading */
     KTimer T;
     T.init(counters != nullptr);
@@ -5019,7 +4514,7 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
                     hipLaunchKernelGGL(k_raygen_single, grid, dim3(256), 0, st, P, dviews, B);
                     T.end(st);
                 } else {
-                    kPrimary[dispatch_g(G)](cn, lds_prim, lds_vis, st, P, dS, dviews, B, tab_p, uni_coh, diff, T);
+                    kPrimary[dispatch_g(G)](cn, lds_prim, lds_ext, st, P, dS, dviews, B, tab_p, uni_coh, diff, T);
                 }
             }
             HIPCHK(hipGetLastError());

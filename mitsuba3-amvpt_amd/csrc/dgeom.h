@@ -34,10 +34,6 @@ struct SceneRef {
     uint32_t n_nodes;
     uint32_t oct_stride;      /* per-lane walks: octant copy o of the nodes at nodes + o * oct_stride (0: one copy) */
     bool uniform;             /* small BVH: the kernels run their kUni = true instance (see trace_closest) */
-    const DNode *tnodes;      /* LDS treelet of the first node ordering (stage_scene kTree), t_n nodes; 0: none */
-    uint32_t t_n;
-    const DNode *onodes;      /* LDS treelets of the 8 octant orderings (stage_scene kOct), o_n nodes each; 0: none */
-    uint32_t o_n;
     bool lds_bvh;             /* nodes / prims are the block's LDS copy (stage_scene), else device memory */
     /* brute-force walks: box meshes screened per lane (DScene::boxes, box_walk) and the other primitives;
      * n_boxes = 0: scan gprims[] (no boxes, or AMVPT_OPT_NO_BOX_SCREEN) */
@@ -56,9 +52,7 @@ struct SceneRef {
 };
 constexpr uint32_t kStk2Stride = 256;   /* the suffix walks' block size: entry k of every thread's stack in one row */
 
-
 struct Hit { float t, u, v; int32_t prim; };
-constexpr uint32_t kNoEnd = 0xffffffffu;   /* treelet walks: the portal's subtree end, not read yet */
 
 AD bool rect_hit(const DPrim &p, const Ray &r, float &t, float &lx, float &ly) {
     /* to_object.transform_affine(ray) then plane z=0 (rectangle.cpp:447-467) */
@@ -80,9 +74,6 @@ AD bool rect_hit(const DPrim &p, const Ray &r, float &t, float &lx, float &ly) {
  * with the same sign, and exceeds maxt when |o.z| > maxt |d.z| (1 + 2^-20) -- the quotient then exceeds
  * maxt (1 + 2^-21) before rounding, so its rounded value does too.  Zero or NaN operands never count as a miss.
  */
-#ifndef AMVPT_RECT_CULL
-#define AMVPT_RECT_CULL 1   /* brute_any skips rectangles its wave certainly misses (A/B) */
-#endif
 AD bool rect_plane_miss(const DPrim &p, const Ray &r) {
     const float oz = fmadd(p.c[2], r.o.z, fmadd(p.c[1], r.o.y, fmadd(p.c[0], r.o.x, p.c[3])));
     const float dz = fmadd(p.c[2], r.d.z, fmadd(p.c[1], r.d.y, p.c[0] * r.d.x));
@@ -106,83 +97,7 @@ AD bool tri_hit(const DPrim &p, const Ray &r, float &t, float &u, float &v) {
 }
 
 /*
- * Packed intersection tests: two (primitive, ray) tests of one primitive type with their arithmetic in
- * v_pk_* pairs -- two primitives against one ray (AMVPT_PAIR_PRIMS) or one primitive against two rays
- * (AMVPT_PAIR_RAYS, the two visibility rays per lane of k_vis).  Element e performs exactly rect_hit's /
- * tri_hit's IEEE operations in the same order (packed FMA, multiply, add and subtract are per-element IEEE;
- * the divisions stay per element), so the hits, t, u and v are the same bits.
- */
-typedef float f2v __attribute__((ext_vector_type(2)));
-AD f2v fma2(f2v a, f2v b, f2v c) { return __builtin_elementwise_fma(a, b, c); }
-struct Hit2 { bool h[2]; float t[2], u[2], v[2]; };
-struct PrimPair { f2v a[4], b[4], c[4]; };
-struct RayPair { f2v ox, oy, oz, dx, dy, dz; float maxt[2]; };
-AD PrimPair prim_pair(const DPrim &p, const DPrim &q) {
-    PrimPair o;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { o.a[k] = f2v{p.a[k], q.a[k]}; o.b[k] = f2v{p.b[k], q.b[k]}; o.c[k] = f2v{p.c[k], q.c[k]}; }
-    return o;
-}
-AD PrimPair prim_pair(const DPrim &p) {
-    PrimPair o;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { o.a[k] = (f2v) p.a[k]; o.b[k] = (f2v) p.b[k]; o.c[k] = (f2v) p.c[k]; }
-    return o;
-}
-AD RayPair ray_pair(const Ray &r) {
-    return RayPair{(f2v) r.o.x, (f2v) r.o.y, (f2v) r.o.z, (f2v) r.d.x, (f2v) r.d.y, (f2v) r.d.z, {r.maxt, r.maxt}};
-}
-AD RayPair ray_pair(const Ray &r0, const Ray &r1) {
-    return RayPair{f2v{r0.o.x, r1.o.x}, f2v{r0.o.y, r1.o.y}, f2v{r0.o.z, r1.o.z},
-                   f2v{r0.d.x, r1.d.x}, f2v{r0.d.y, r1.d.y}, f2v{r0.d.z, r1.d.z}, {r0.maxt, r1.maxt}};
-}
-AD Hit2 rect_hit2(const PrimPair &P, const RayPair &R) {
-    const f2v lox = fma2(P.a[2], R.oz, fma2(P.a[1], R.oy, fma2(P.a[0], R.ox, P.a[3])));
-    const f2v loy = fma2(P.b[2], R.oz, fma2(P.b[1], R.oy, fma2(P.b[0], R.ox, P.b[3])));
-    const f2v loz = fma2(P.c[2], R.oz, fma2(P.c[1], R.oy, fma2(P.c[0], R.ox, P.c[3])));
-    const f2v ldx = fma2(P.a[2], R.dz, fma2(P.a[1], R.dy, P.a[0] * R.dx));
-    const f2v ldy = fma2(P.b[2], R.dz, fma2(P.b[1], R.dy, P.b[0] * R.dx));
-    const f2v ldz = fma2(P.c[2], R.dz, fma2(P.c[1], R.dy, P.c[0] * R.dx));
-    Hit2 o;
-#pragma unroll
-    for (int e = 0; e < 2; ++e) o.t[e] = -loz[e] / ldz[e];
-    /* the local hit point (lx = fma(dx, t, ox) per element) */
-    const f2v tt = {o.t[0], o.t[1]};
-    const f2v lx = fma2(ldx, tt, lox), ly = fma2(ldy, tt, loy);
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-        o.u[e] = lx[e];
-        o.v[e] = ly[e];
-        o.h[e] = o.t[e] >= 0.f && o.t[e] <= R.maxt[e] && fabs_(lx[e]) <= 1.f && fabs_(ly[e]) <= 1.f;
-    }
-    return o;
-}
-AD Hit2 tri_hit2(const PrimPair &P, const RayPair &R) {
-    /* p0 = a, e1 = b, e2 = c; pvec = cross(d, e2) with fmsub(a, b, c) = fma(a, b, -c) */
-    const f2v pvx = fma2(R.dy, P.c[2], -(R.dz * P.c[1])), pvy = fma2(R.dz, P.c[0], -(R.dx * P.c[2])),
-              pvz = fma2(R.dx, P.c[1], -(R.dy * P.c[0]));
-    const f2v det = fma2(P.b[2], pvz, fma2(P.b[1], pvy, P.b[0] * pvx));
-    f2v inv;
-    inv[0] = 1.0f / det[0];
-    inv[1] = 1.0f / det[1];
-    const f2v tvx = R.ox - P.a[0], tvy = R.oy - P.a[1], tvz = R.oz - P.a[2];
-    const f2v u = fma2(tvz, pvz, fma2(tvy, pvy, tvx * pvx)) * inv;
-    const f2v qx = fma2(tvy, P.b[2], -(tvz * P.b[1])), qy = fma2(tvz, P.b[0], -(tvx * P.b[2])),
-              qz = fma2(tvx, P.b[1], -(tvy * P.b[0]));
-    const f2v v = fma2(R.dz, qz, fma2(R.dy, qy, R.dx * qx)) * inv;
-    const f2v t = fma2(P.c[2], qz, fma2(P.c[1], qy, P.c[0] * qx)) * inv;
-    const f2v uv = u + v;
-    Hit2 o;
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-        o.t[e] = t[e]; o.u[e] = u[e]; o.v[e] = v[e];
-        o.h[e] = u[e] >= 0.f && u[e] <= 1.f && v[e] >= 0.f && uv[e] <= 1.f && t[e] >= 0.f && t[e] <= R.maxt[e];
-    }
-    return o;
-}
-
-/*
- * f32 screen in front of the float64 sphere test (AMVPT_SPHERE_SCREEN): false only when the exact test
+ * f32 screen in front of the float64 sphere test: false only when the exact test
  * cannot hit, so a dropped ray returns what the exact test would (no hit, t = inf) and the results are the
  * same bits; NaN keeps the ray.
  * Line: the exact test hits only if its discriminant B^2 - 4AC >= 0, i.e. (up to f64 rounding, ~1e-16
@@ -191,20 +106,12 @@ AD Hit2 tri_hit2(const PrimPair &P, const RayPair &R) {
  * h^2 |d|^2 = |l x d|^2 -- the cross-product form, whose f32 error near h = r is <~ 8u |l| r |d|^2 (no
  * cancellation of |l|^2 terms) -- and the ray is dropped only if h^2 > R2 = r^2 (1 + 1e-5) +
  * 2e-5 r s + 4e-12 s^2 (s = sqrt(2 (|o|^2 + |l|^2)) >= |o| + |l|): over 10x the error and eps terms.
- * Segment (AMVPT_SPHERE_SCREEN 2): the sphere of radius^2 R2 meets the line over the parameters tc -+ th
+ * Segment: the sphere of radius^2 R2 meets the line over the parameters tc -+ th
  * (tc = -l.d / |d|^2, th = sqrt(R2 - h^2) / |d|), which contain the exact test's entry and exit parameters
  * (plane_t + x0 / x1) up to errors below m = 2e-5 (|tc| + |l| / |d|); the ray is dropped when that range
  * lies beyond [0, maxt] by m.  A shadow ray toward a point on a sphere light stops ShadowEpsilon ~ 9e-4 of
  * its length short of it (spawn_ray_to), so the target light's own exact test is dropped too.
  */
-#ifndef AMVPT_SPHERE_SCREEN
-#define AMVPT_SPHERE_SCREEN 2   /* 1: the line test only, 0: off (A/B) */
-#endif
-#ifndef AMVPT_SPHERE_DEFER
-/* 1: the wave-uniform walks of scenes with <= 64 spheres and the brute-force walks defer the float64 tests
- * past the walk (kSph = 2 below, brute_closest / brute_any); 0: in place (A/B) */
-#define AMVPT_SPHERE_DEFER 1
-#endif
 AD bool sphere_maybe(const DPrim &p, const Ray &ray) {
     const float lx = ray.o.x - p.a[0], ly = ray.o.y - p.a[1], lz = ray.o.z - p.a[2], r = p.a[3];
     const f3 d = ray.d;
@@ -216,20 +123,17 @@ AD bool sphere_maybe(const DPrim &p, const Ray &ray) {
     const float sc = __builtin_amdgcn_sqrtf(2.f * (oo + ll));
     const float R2 = fmadd(r * r, 1.00001f, fmadd(2e-5f * r, sc, 4e-12f * (sc * sc)));
     if (E > dd * R2) return false;
-    if (AMVPT_SPHERE_SCREEN >= 2) {
-        const float ld = fmadd(lz, d.z, fmadd(ly, d.y, lx * d.x));
-        const float idd = __builtin_amdgcn_rcpf(dd);
-        const float tc = -ld * idd;
-        const float th = __builtin_amdgcn_sqrtf(fmaxf(fmadd(dd, R2, -E), 0.f)) * idd * 1.0001f;
-        const float m = 2e-5f * (fabs_(tc) + __builtin_amdgcn_sqrtf(ll * idd));
-        if (tc - th > ray.maxt + m || tc + th < -m) return false;
-    }
-    return true;
+    const float ld = fmadd(lz, d.z, fmadd(ly, d.y, lx * d.x));
+    const float idd = __builtin_amdgcn_rcpf(dd);
+    const float tc = -ld * idd;
+    const float th = __builtin_amdgcn_sqrtf(fmaxf(fmadd(dd, R2, -E), 0.f)) * idd * 1.0001f;
+    const float m = 2e-5f * (fabs_(tc) + __builtin_amdgcn_sqrtf(ll * idd));
+    return !(tc - th > ray.maxt + m || tc + th < -m);
 }
 
 /* float64 sphere test, as the llvm variants compute it (sphere.cpp:460-518) */
 AD bool sphere_hit(const DPrim &p, const Ray &ray, float &t_out) {
-    if (AMVPT_SPHERE_SCREEN && !sphere_maybe(p, ray)) {
+    if (!sphere_maybe(p, ray)) {
         t_out = kInf;
         return false;
     }
@@ -281,27 +185,11 @@ AD bool prim_hit(const DPrim &p, const Ray &r, float &t, float &u, float &v) {
  * primitives get the exact test, never a hit -- so it runs on a 1-ulp reciprocal and the fused
  * form t = lo * inv - o * inv (one rounding of o * inv: an error far below the pad in t units
  * for origins within 1000x the scene's extent); a NaN slab (0 * inf) drops out of the min/max
- * and only widens the box.  AMVPT_EXACT_BOX=1 restores (lo - o) / d (A/B).
+ * and only widens the box.
  */
-#ifndef AMVPT_EXACT_BOX
-#define AMVPT_EXACT_BOX 0
-#endif
 struct BoxRay { f3 o, inv, oinv; };
-/* per-lane walk of the suffix kernels (k_extend, k_shadow): 2 speculative while-while, 1 plain
- * while-while, 0 one loop (A/B) */
-#ifndef AMVPT_WALK_WW
-#define AMVPT_WALK_WW 2
-#endif
-/* the while-while node step's leaf bookkeeping as selects instead of nested branches (0: branches, A/B) */
-#ifndef AMVPT_WALK_SEL
-#define AMVPT_WALK_SEL 1
-#endif
 AD float box_rcp(float d) {
-#if AMVPT_EXACT_BOX
-    return 1.f / (d != 0.f ? d : mulsign(1e-30f, d));
-#else
     return __builtin_amdgcn_rcpf(fabs_(d) >= 1e-30f ? d : mulsign(1e-30f, d));
-#endif
 }
 AD BoxRay box_ray(const Ray &r) {
     BoxRay b;
@@ -311,15 +199,9 @@ AD BoxRay box_ray(const Ray &r) {
     return b;
 }
 AD bool box_hit(const DNode &n, const BoxRay &b, float tmax) {
-#if AMVPT_EXACT_BOX
-    float tx0 = (n.lo[0] - b.o.x) * b.inv.x, tx1 = (n.hi[0] - b.o.x) * b.inv.x;
-    float ty0 = (n.lo[1] - b.o.y) * b.inv.y, ty1 = (n.hi[1] - b.o.y) * b.inv.y;
-    float tz0 = (n.lo[2] - b.o.z) * b.inv.z, tz1 = (n.hi[2] - b.o.z) * b.inv.z;
-#else
     float tx0 = fmaf(n.lo[0], b.inv.x, -b.oinv.x), tx1 = fmaf(n.hi[0], b.inv.x, -b.oinv.x);
     float ty0 = fmaf(n.lo[1], b.inv.y, -b.oinv.y), ty1 = fmaf(n.hi[1], b.inv.y, -b.oinv.y);
     float tz0 = fmaf(n.lo[2], b.inv.z, -b.oinv.z), tz1 = fmaf(n.hi[2], b.inv.z, -b.oinv.z);
-#endif
     float tmin = fmaxf(fmaxf(fminf(tx0, tx1), fminf(ty0, ty1)), fmaxf(fminf(tz0, tz1), 0.f));
     float tm = fminf(fminf(fmaxf(tx0, tx1), fmaxf(ty0, ty1)), fminf(fmaxf(tz0, tz1), tmax));
     return tmin <= tm;
@@ -370,9 +252,6 @@ template <typename T, int AS> AD T load_as(const T *base, uint32_t idx) {
     return out;
 }
 template <typename T> AD T load_lds(const T *base, uint32_t idx) { return load_as<T, 3>(base, idx); }
-#ifndef AMVPT_WALK_AS
-#define AMVPT_WALK_AS 1   /* per-lane walks read nodes / primitives through explicit address spaces (0: generic, A/B) */
-#endif
 template <typename T> AD T load_global(const T *base, uint32_t idx) { return load_as<T, 1>(base, idx); }
 
 /* Primitive test with a wave-uniform primitive type (no divergence between shapes). */
@@ -451,70 +330,6 @@ AD bool outer_any(const SceneRef &sc, const Ray &ray, bool skip) {
     return found;
 }
 
-/*
- * Closest hit over the octant treelets (per-lane walks of large BVHs): the ray's direction-octant
- * ordering starts in its LDS treelet and continues at a portal in the same ordering's global copy
- * (indices local to the copy), returning to the treelet at the end of the portal's subtree.  The node
- * sequence is the global walk's, so the hit is the same; speculative while-while as trace_closest.
- */
-AD Hit trace_closest_tl(const SceneRef &sc, const Ray &ray, Hit best, uint32_t best_orig) {
-    const BoxRay br = box_ray(ray);
-    float tmax_box = fminf(ray.maxt, best.t);
-    const uint32_t o = (fbits(ray.d.x) >> 31) | ((fbits(ray.d.y) >> 31) << 1) | ((fbits(ray.d.z) >> 31) << 2);
-    const DNode *const tn = sc.onodes + (size_t) o * sc.o_n;
-    const DNode *const gn = sc.gnodes + (size_t) o * sc.oct_stride;
-    auto leaf_test = [&](uint32_t first, uint32_t count) {
-        for (uint32_t i = 0; i < count; ++i) {
-            const uint32_t pi = first + i;
-            const DPrim p = load_global(sc.gprims, pi);
-            float t, u, v;
-            if (prim_hit(p, ray, t, u, v)) {
-                if (t < best.t || (t == best.t && p.pad < best_orig)) {
-                    best.t = t; best.u = u; best.v = v; best.prim = (int32_t) pi;
-                    best_orig = p.pad;
-                    tmax_box = t;
-                }
-            }
-        }
-    };
-    const uint32_t nt = sc.o_n;
-    uint32_t node = 0, gend = 0, tres = 0;
-    bool glob = false;
-    for (;;) {
-        uint32_t lf = 0, lc = 0;
-        bool stop = false;
-        for (;;) {
-            const bool open = glob || node < nt;
-            if (!wave_any(open && lc == 0u)) break;
-            if (open && !stop) {
-                DNode n;
-                if (glob) n = load_global(gn, node);
-                else n = load_lds(tn, node);
-                if (glob && gend == kNoEnd) gend = n.skip_count & kNodeSkipMask;   /* the portal's own node */
-                const bool hit = box_hit(n, br, tmax_box);
-                const uint32_t count = n.skip_count >> kNodeCountShift, skip = n.skip_count & kNodeSkipMask;
-                uint32_t next;
-                if (hit && count) {
-                    if (lc == 0u) { lf = n.first; lc = count; next = skip; }
-                    else { stop = true; next = node; }
-                } else if (hit && !glob && (n.first & kPortal)) {
-                    tres = skip;
-                    glob = true;
-                    gend = kNoEnd;
-                    next = n.first & ~kPortal;
-                } else {
-                    next = hit ? node + 1 : skip;
-                }
-                if (glob && next == gend) { glob = false; next = tres; }
-                node = next;
-            }
-        }
-        if (!wave_any(lc != 0u)) break;
-        leaf_test(lf, lc);
-    }
-    return best;
-}
-
 template <bool kSph> AD bool prim_hit_b(const DPrim &p, uint32_t type, const Ray &r, float &t, float &u, float &v);
 /* the per-lane walks' leaf test: kSph -1 a triangle-only BVH (no type dispatch), 0 no spheres, 1 any */
 template <int kSph> AD bool prim_hit_l(const DPrim &p, const Ray &r, float &t, float &u, float &v) {
@@ -526,7 +341,6 @@ template <bool kUni, int kWW = 0, int kSph = 1> AD Hit trace_closest(const Scene
     Hit best{kInf, 0.f, 0.f, -1};
     uint32_t best_orig = 0xffffffffu;
     outer_closest(sc, ray, best, best_orig);
-    if (!kUni && sc.o_n) return trace_closest_tl(sc, ray, best, best_orig);
     const BoxRay br = box_ray(ray);
     float tmax_box = fminf(ray.maxt, best.t);
     if (kUni) {
@@ -589,14 +403,11 @@ template <bool kUni, int kWW = 0, int kSph = 1> AD Hit trace_closest(const Scene
      * spaces (not the generic SceneRef pointers, which made every node and primitive read a flat load) */
     auto walk = [&](auto lds_tag) -> Hit {
         constexpr bool kL = decltype(lds_tag)::value;
-        auto ld_node = [&](uint32_t i) {
-            if (!AMVPT_WALK_AS) return nodes[i];
-            return kL ? load_lds(nodes, i) : load_global(nodes, i);
-        };
+        auto ld_node = [&](uint32_t i) { return kL ? load_lds(nodes, i) : load_global(nodes, i); };
         auto leaf_test = [&](uint32_t first, uint32_t count) {
             for (uint32_t i = 0; i < count; ++i) {
                 const uint32_t pi = first + i;
-                const DPrim p = !AMVPT_WALK_AS ? sc.prims[pi] : kL ? load_lds(sc.prims, pi) : load_global(sc.prims, pi);
+                const DPrim p = kL ? load_lds(sc.prims, pi) : load_global(sc.prims, pi);
                 float t, u, v;
                 if (prim_hit_l<kSph>(p, ray, t, u, v)) {
                     if (t < best.t || (t == best.t && p.pad < best_orig)) {
@@ -625,21 +436,12 @@ template <bool kUni, int kWW = 0, int kSph = 1> AD Hit trace_closest(const Scene
                     const DNode n = ld_node(node);
                     const bool hit = box_hit(n, br, tmax_box);
                     const uint32_t count = n.skip_count >> kNodeCountShift, skip = n.skip_count & kNodeSkipMask;
-#if AMVPT_WALK_SEL
                     /* one branch per step: the leaf bookkeeping as selects */
                     const bool leaf = hit && count != 0u, take = leaf && lc == 0u;
                     stop = leaf && !take;   /* the second leaf: revisit it next round */
                     lf = take ? n.first : lf;
                     lc = take ? count : lc;
                     node = (hit && count == 0u) ? node + 1 : (stop ? node : skip);
-#else
-                    if (hit && count) {
-                        if (lc == 0u) { lf = n.first; lc = count; node = skip; }
-                        else stop = true;   /* the second leaf: revisit it next round */
-                    } else {
-                        node = hit ? node + 1 : skip;
-                    }
-#endif
                 }
             }
             if (!wave_any(lc != 0u)) break;
@@ -659,133 +461,8 @@ template <bool kUni, int kWW = 0, int kSph = 1> AD Hit trace_closest(const Scene
     return sc.lds_bvh ? walk(std::true_type{}) : walk(std::false_type{});
 }
 
-/*
- * Any-hit walks over an LDS treelet (large BVHs, DScene::tnodes): the top levels of the first node
- * ordering sit in LDS (staged per block), so the first node visits of a walk -- the ones every ray makes
- * -- are LDS reads instead of dependent loads from L2; a portal (a treelet node whose children lie below
- * the cut) continues the threaded walk in the global array at the same node, whose skip link is the end
- * of its subtree, and the walk returns to the treelet there.  The nodes tested are the same as the
- * global walk's (same boxes, same order), so the verdict is the same.
- */
-AD bool trace_any_tl(const SceneRef &sc, const Ray &ray, bool found = false) {
-    const BoxRay br = box_ray(ray);
-    auto leaf_any = [&](uint32_t first, uint32_t count) {
-        bool f = false;
-        for (uint32_t i = 0; i < count && !f; ++i) {
-            const DPrim p = load_global(sc.gprims, first + i);
-            float t, u, v;
-            f = prim_hit(p, ray, t, u, v);
-        }
-        return f;
-    };
-    const uint32_t nt = sc.t_n;
-    uint32_t node = 0, gend = 0, tres = 0;
-    bool glob = false;
-    /* speculative while-while (trace_any kWW = 2): a lane holding a leaf steps on until the wave's
-     * other lanes hold one too, and stops at a second leaf */
-    for (;;) {
-        uint32_t lf = 0, lc = 0;
-        bool stop = false;
-        for (;;) {
-            const bool open = !found && (glob || node < nt);
-            if (!wave_any(open && lc == 0u)) break;
-            if (open && !stop) {
-                DNode n;
-                if (glob) n = load_global(sc.gnodes, node);
-                else n = load_lds(sc.tnodes, node);
-                if (glob && gend == kNoEnd) gend = n.skip_count & kNodeSkipMask;   /* the portal's own node */
-                const bool hit = box_hit(n, br, ray.maxt);
-                const uint32_t count = n.skip_count >> kNodeCountShift, skip = n.skip_count & kNodeSkipMask;
-                uint32_t next;
-                if (hit && count) {
-                    if (lc == 0u) { lf = n.first; lc = count; next = skip; }
-                    else { stop = true; next = node; }   /* the second leaf: revisit it next round */
-                } else if (hit && !glob && (n.first & kPortal)) {
-                    tres = skip;
-                    glob = true;
-                    gend = kNoEnd;
-                    next = n.first & ~kPortal;
-                } else {
-                    next = hit ? node + 1 : skip;
-                }
-                if (glob && next == gend) { glob = false; next = tres; }
-                node = next;
-            }
-        }
-        if (!wave_any(lc != 0u)) break;
-        if (lc) found = found || leaf_any(lf, lc);
-    }
-    return found;
-}
-
-/* the wave-uniform any-hit walk over the treelet for one or two rays per lane (trace_any<true> /
- * trace_any2_uni): the treelet node is one LDS broadcast read per wave */
-AD void trace_any_uni_tl(const SceneRef &sc, const Ray &r0, bool act0, const Ray &r1, bool act1, bool two, bool &f0,
-                         bool &f1) {
-    const BoxRay b0 = box_ray(r0), b1 = box_ray(r1);
-    f0 = !act0;
-    f1 = !act1 || !two;
-    f0 = f0 || outer_any(sc, r0, f0);
-    f1 = f1 || outer_any(sc, r1, f1);
-    const uint32_t nt = ufirst(sc.t_n);
-    uint32_t t = 0, g = 0, gend = 0, tres = 0;
-    bool glob = false;
-    for (;;) {
-        DNode n;
-        if (!glob) {
-            if (t >= nt) break;
-            n = load_lds(sc.tnodes, t);
-        } else {
-            n = load_uniform(sc.gnodes, g);
-            if (gend == kNoEnd) gend = ufirst(n.skip_count) & kNodeSkipMask;
-        }
-        const bool enter = wave_any((!f0 && box_hit(n, b0, r0.maxt)) || (!f1 && box_hit(n, b1, r1.maxt)));
-        const uint32_t skc = ufirst(n.skip_count), first = ufirst(n.first);
-        const uint32_t count = skc >> kNodeCountShift, skip = skc & kNodeSkipMask;
-        if (enter && count) {
-            for (uint32_t i = 0; i < count; ++i) {
-                const DPrim p = load_uniform(sc.gprims, first + i);
-                const uint32_t type = ufirst(p.type);
-                float tt, u, v;
-                const bool h0 = prim_hit_u(p, type, r0, tt, u, v);
-                f0 = f0 || h0;
-                if (two) {
-                    const bool h1 = prim_hit_u(p, type, r1, tt, u, v);
-                    f1 = f1 || h1;
-                }
-            }
-            if (!wave_any(!f0 || !f1)) break;
-        }
-        if (enter && !count && !glob && (first & kPortal)) {
-            tres = skip;
-            glob = true;
-            gend = kNoEnd;
-            g = first & ~kPortal;
-            continue;
-        }
-        const uint32_t cur = glob ? g : t;
-        const uint32_t next = (enter && !count) ? cur + 1 : skip;
-        if (glob) {
-            if (next == gend) { glob = false; t = tres; }
-            else g = next;
-        } else {
-            t = next;
-        }
-    }
-    f0 = f0 && act0;
-    f1 = f1 && act1 && two;
-}
-
 /* Any hit in [0, maxt] (Scene::ray_test); same two walks as trace_closest. */
 template <bool kUni, int kWW = 0, int kSph = 1> AD bool trace_any(const SceneRef &sc, const Ray &ray) {
-    if (sc.t_n) {
-        if (kUni) {
-            bool f0, f1;
-            trace_any_uni_tl(sc, ray, true, ray, false, false, f0, f1);
-            return f0;
-        }
-        return trace_any_tl(sc, ray, outer_any(sc, ray, false));
-    }
     const BoxRay br = box_ray(ray);
     const bool outer_found = outer_any(sc, ray, false);
     if (kUni) {
@@ -831,15 +508,11 @@ template <bool kUni, int kWW = 0, int kSph = 1> AD bool trace_any(const SceneRef
      * kL: LDS-staged BVH, else device memory (explicit address spaces, see trace_closest) */
     auto walk = [&](auto lds_tag) -> bool {
         constexpr bool kL = decltype(lds_tag)::value;
-        auto ld_node = [&](uint32_t i) {
-            if (!AMVPT_WALK_AS) return sc.nodes[i];
-            return kL ? load_lds(sc.nodes, i) : load_global(sc.nodes, i);
-        };
+        auto ld_node = [&](uint32_t i) { return kL ? load_lds(sc.nodes, i) : load_global(sc.nodes, i); };
         auto leaf_any = [&](uint32_t first, uint32_t count) {
             bool f = false;
             for (uint32_t i = 0; i < count && !f; ++i) {
-                const DPrim p = !AMVPT_WALK_AS ? sc.prims[first + i]
-                                : kL ? load_lds(sc.prims, first + i) : load_global(sc.prims, first + i);
+                const DPrim p = kL ? load_lds(sc.prims, first + i) : load_global(sc.prims, first + i);
                 float t, u, v;
                 f = prim_hit_l<kSph>(p, ray, t, u, v);
             }
@@ -858,20 +531,11 @@ template <bool kUni, int kWW = 0, int kSph = 1> AD bool trace_any(const SceneRef
                     const DNode n = ld_node(node);
                     const bool hit = box_hit(n, br, ray.maxt);
                     const uint32_t count = n.skip_count >> kNodeCountShift, skip = n.skip_count & kNodeSkipMask;
-#if AMVPT_WALK_SEL
                     const bool leaf = hit && count != 0u, take = leaf && lc == 0u;
                     stop = leaf && !take;
                     lf = take ? n.first : lf;
                     lc = take ? count : lc;
                     node = (hit && count == 0u) ? node + 1 : (stop ? node : skip);
-#else
-                    if (hit && count) {
-                        if (lc == 0u) { lf = n.first; lc = count; node = skip; }
-                        else stop = true;
-                    } else {
-                        node = hit ? node + 1 : skip;
-                    }
-#endif
                 }
             }
             if (!wave_any(lc != 0u)) break;
@@ -923,20 +587,13 @@ AD void stk_store(uint32_t *stk, uint32_t k, uint32_t v) {
     ((lu32 *) (uint32_t) (uintptr_t) stk)[k * kStk2Stride] = v;
 }
 constexpr uint32_t kRef2End = 0x7fffffffu;   /* no node (an inner index never reaches it) */
-/* the 32-B float16 nodes (dscene.h DNode2h) instead of the 64-B float ones: half the bytes per node step (A/B) */
-#ifndef AMVPT_TRI_LOAD48
-#define AMVPT_TRI_LOAD48 1   /* the two-box walks of triangle-only BVHs load 48 / 52 B of a leaf triangle (0: 64, A/B) */
-#endif
-#ifndef AMVPT_BVH2_HALF
-#define AMVPT_BVH2_HALF 1
-#endif
+/* the walks read the 32-B float16 nodes (dscene.h DNode2h), not the 64-B float ones: half the bytes per node step */
 AD void half2_unpack(uint32_t w, float &a, float &b) {
     a = (float) __builtin_bit_cast(_Float16, (uint16_t) (w & 0xffffu));
     b = (float) __builtin_bit_cast(_Float16, (uint16_t) (w >> 16));
 }
 /* the walk's ray: in the float16 nodes' normalized frame (same t: origin and direction scale together) */
 AD BoxRay box2_ray(const SceneRef &sc, const Ray &r) {
-    if (!AMVPT_BVH2_HALF) return box_ray(r);
     const DScene &S = *sc.g;
     const float s = S.n2_scale;
     const Ray q{mk((r.o.x - S.n2_center[0]) * s, (r.o.y - S.n2_center[1]) * s, (r.o.z - S.n2_center[2]) * s),
@@ -946,18 +603,10 @@ AD BoxRay box2_ray(const SceneRef &sc, const Ray &r) {
 /* one step of a two-box walk at inner node `cur`: enter the nearer hit child, stack the farther one */
 AD uint32_t node2_step(const SceneRef &sc, uint32_t cur, const BoxRay &br, float tmax, uint32_t &sp) {
     float bx[12];
-    uint32_t r0, r1;
-    if (AMVPT_BVH2_HALF) {
-        const DNode2h n = load_global(sc.g->nodes2h, cur);
+    const DNode2h n = load_global(sc.g->nodes2h, cur);
 #pragma unroll
-        for (int w = 0; w < 6; ++w) half2_unpack(n.h[w], bx[2 * w], bx[2 * w + 1]);
-        r0 = n.ref[0]; r1 = n.ref[1];
-    } else {
-        const DNode2 n = load_global(sc.nodes2, cur);
-#pragma unroll
-        for (int k = 0; k < 12; ++k) bx[k] = n.b[k];
-        r0 = n.ref[0]; r1 = n.ref[1];
-    }
+    for (int w = 0; w < 6; ++w) half2_unpack(n.h[w], bx[2 * w], bx[2 * w + 1]);
+    const uint32_t r0 = n.ref[0], r1 = n.ref[1];
     float t0, t1;
     const bool h0 = box2_hit(bx, br, tmax, t0), h1 = box2_hit(bx + 6, br, tmax, t1);
     const bool sw = h1 && (!h0 || t1 < t0);
@@ -970,7 +619,7 @@ AD uint32_t node2_step(const SceneRef &sc, uint32_t cur, const BoxRay &br, float
  * (closest hit: kPad) the scene-order index only -- 48 / 52 of its 64 B (the walks are bound by the bytes their
  * divergent gathers return, see above); other BVHs read the whole record */
 template <int kSph, bool kPad> AD DPrim leaf_prim(const SceneRef &sc, uint32_t i) {
-    if constexpr (kSph < 0 && AMVPT_TRI_LOAD48) {
+    if constexpr (kSph < 0) {
         typedef float v4f __attribute__((ext_vector_type(4)));
         typedef __attribute__((address_space(1))) const v4f gv4f;
         typedef __attribute__((address_space(1))) const uint32_t gu32;
@@ -1065,16 +714,9 @@ template <int kSph> AD bool trace_any2(const SceneRef &sc, const Ray &ray, bool 
  * once per two rays.  Lanes without a ray pass act = false (they count as found).  Exact for the
  * same reason as trace_any: a primitive tested for a ray whose box test failed cannot hit it.
  */
-#ifndef AMVPT_PAIR_RAYS
-/* 1: trace_any2_uni tests a primitive against both rays as one packed test -- off: config-M k_vis 63.2 ->
- * 79.0 ms, C3 232 -> 284 ms (r04e; 48 B of scratch and the pair moves outweigh the packed arithmetic) */
-#define AMVPT_PAIR_RAYS 0
-#endif
 template <int kSph = 1>
 AD void trace_any2_uni(const SceneRef &sc, const Ray &r0, bool act0, const Ray &r1, bool act1, bool &f0, bool &f1) {
-    if (sc.t_n) { trace_any_uni_tl(sc, r0, act0, r1, act1, true, f0, f1); return; }
     const BoxRay b0 = box_ray(r0), b1 = box_ray(r1);
-    const RayPair R2 = ray_pair(r0, r1);
     const uint32_t nn = ufirst(sc.n_nodes);
     f0 = !act0; f1 = !act1;
     f0 = f0 || outer_any(sc, r0, f0);
@@ -1093,13 +735,6 @@ AD void trace_any2_uni(const SceneRef &sc, const Ray &r0, bool act0, const Ray &
                 const uint32_t type = ufirst(p.type);
                 if (kSph == 2 && type == PRIM_SPHERE) {
                     if (wave_any((!f0 && sphere_maybe(p, r0)) || (!f1 && sphere_maybe(p, r1)))) dm |= 1ull << ufirst(p.face);
-                    continue;
-                }
-                if (AMVPT_PAIR_RAYS && type != PRIM_SPHERE) {
-                    /* both rays against the primitive as one packed test */
-                    const Hit2 h = type == PRIM_RECT ? rect_hit2(prim_pair(p), R2) : tri_hit2(prim_pair(p), R2);
-                    f0 = f0 || h.h[0];
-                    f1 = f1 || h.h[1];
                     continue;
                 }
                 float t, u, v;
@@ -1124,179 +759,6 @@ AD void trace_any2_uni(const SceneRef &sc, const Ray &r0, bool act0, const Ray &
     }
     f0 = f0 && act0;
     f1 = f1 && act1;
-}
-
-/*
- * Per-lane walks of two rays per thread (AMVPT_SHADOW_RAYS / AMVPT_EXTEND_RAYS = 2, the suffix walks of large
- * BVHs): the speculative while-while walk of trace_any / trace_closest for each ray, stepped together -- the
- * two node loads of a step are issued back to back, so a thread keeps two dependent-load chains in flight.
- * Each ray visits exactly the nodes and primitives its single walk visits, so the results are the same.
- */
-struct LaneWalk { uint32_t node, lf, lc; bool stop; };
-AD void lane_step(const DNode &n, const BoxRay &b, float tmax, LaneWalk &w) {
-    const bool hit = box_hit(n, b, tmax);
-    const uint32_t count = n.skip_count >> kNodeCountShift, skip = n.skip_count & kNodeSkipMask;
-    if (hit && count) {
-        if (w.lc == 0u) { w.lf = n.first; w.lc = count; w.node = skip; }
-        else w.stop = true;   /* the second leaf: revisit it next round */
-    } else {
-        w.node = hit ? w.node + 1 : skip;
-    }
-}
-template <int kSph = 1>
-AD void trace_any_lane2(const SceneRef &sc, const Ray &r0, bool act0, const Ray &r1, bool act1, bool &f0, bool &f1) {
-    const BoxRay b0 = box_ray(r0), b1 = box_ray(r1);
-    auto walk = [&](auto lds_tag) {
-        constexpr bool kL = decltype(lds_tag)::value;
-        auto ld_node = [&](uint32_t i) { return kL ? load_lds(sc.nodes, i) : load_global(sc.nodes, i); };
-        auto leaf_any = [&](const Ray &ray, uint32_t first, uint32_t count) {
-            bool f = false;
-            for (uint32_t i = 0; i < count && !f; ++i) {
-                const DPrim p = kL ? load_lds(sc.prims, first + i) : load_global(sc.prims, first + i);
-                float t, u, v;
-                f = prim_hit_l<kSph>(p, ray, t, u, v);
-            }
-            return f;
-        };
-        const uint32_t nn = sc.n_nodes;
-        LaneWalk w0{act0 ? 0u : nn, 0u, 0u, false}, w1{act1 ? 0u : nn, 0u, 0u, false};
-        bool h0 = outer_any(sc, r0, !act0), h1 = outer_any(sc, r1, !act1);
-        for (;;) {
-            w0.lf = w0.lc = w1.lf = w1.lc = 0u;
-            w0.stop = w1.stop = false;
-            for (;;) {
-                const bool need = (!h0 && w0.lc == 0u && w0.node < nn) || (!h1 && w1.lc == 0u && w1.node < nn);
-                if (!wave_any(need)) break;
-                const bool s0 = !h0 && w0.node < nn && !w0.stop, s1 = !h1 && w1.node < nn && !w1.stop;
-                DNode n0, n1;
-                if (s0) n0 = ld_node(w0.node);
-                if (s1) n1 = ld_node(w1.node);
-                if (s0) lane_step(n0, b0, r0.maxt, w0);
-                if (s1) lane_step(n1, b1, r1.maxt, w1);
-            }
-            if (!wave_any(w0.lc != 0u || w1.lc != 0u)) break;
-            if (w0.lc) h0 = h0 || leaf_any(r0, w0.lf, w0.lc);
-            if (w1.lc) h1 = h1 || leaf_any(r1, w1.lf, w1.lc);
-        }
-        f0 = h0 && act0;
-        f1 = h1 && act1;
-    };
-    if (sc.lds_bvh) walk(std::true_type{});
-    else walk(std::false_type{});
-}
-
-template <int kSph = 1>
-AD void trace_closest_lane2(const SceneRef &sc, const Ray &r0, bool act0, const Ray &r1, bool act1, Hit &o0, Hit &o1) {
-    const BoxRay b0 = box_ray(r0), b1 = box_ray(r1);
-    const DNode *const nodes0 = octant_nodes(sc, r0.d), *const nodes1 = octant_nodes(sc, r1.d);
-    Hit best0{kInf, 0.f, 0.f, -1}, best1{kInf, 0.f, 0.f, -1};
-    uint32_t orig0 = 0xffffffffu, orig1 = 0xffffffffu;
-    outer_closest(sc, r0, best0, orig0);
-    outer_closest(sc, r1, best1, orig1);
-    float tmax0 = fminf(r0.maxt, best0.t), tmax1 = fminf(r1.maxt, best1.t);
-    auto walk = [&](auto lds_tag) {
-        constexpr bool kL = decltype(lds_tag)::value;
-        auto ld_node = [&](const DNode *nodes, uint32_t i) { return kL ? load_lds(nodes, i) : load_global(nodes, i); };
-        auto leaf_test = [&](const Ray &ray, uint32_t first, uint32_t count, Hit &best, uint32_t &best_orig, float &tmax) {
-            for (uint32_t i = 0; i < count; ++i) {
-                const uint32_t pi = first + i;
-                const DPrim p = kL ? load_lds(sc.prims, pi) : load_global(sc.prims, pi);
-                float t, u, v;
-                if (prim_hit_l<kSph>(p, ray, t, u, v)) {
-                    if (t < best.t || (t == best.t && p.pad < best_orig)) {
-                        best.t = t; best.u = u; best.v = v; best.prim = (int32_t) pi;
-                        best_orig = p.pad;
-                        tmax = t;
-                    }
-                }
-            }
-        };
-        const uint32_t nn = sc.n_nodes;
-        LaneWalk w0{act0 ? 0u : nn, 0u, 0u, false}, w1{act1 ? 0u : nn, 0u, 0u, false};
-        for (;;) {
-            w0.lf = w0.lc = w1.lf = w1.lc = 0u;
-            w0.stop = w1.stop = false;
-            for (;;) {
-                const bool need = (w0.lc == 0u && w0.node < nn) || (w1.lc == 0u && w1.node < nn);
-                if (!wave_any(need)) break;
-                const bool s0 = w0.node < nn && !w0.stop, s1 = w1.node < nn && !w1.stop;
-                DNode n0, n1;
-                if (s0) n0 = ld_node(nodes0, w0.node);
-                if (s1) n1 = ld_node(nodes1, w1.node);
-                if (s0) lane_step(n0, b0, tmax0, w0);
-                if (s1) lane_step(n1, b1, tmax1, w1);
-            }
-            if (!wave_any(w0.lc != 0u || w1.lc != 0u)) break;
-            if (w0.lc) leaf_test(r0, w0.lf, w0.lc, best0, orig0, tmax0);
-            if (w1.lc) leaf_test(r1, w1.lf, w1.lc, best1, orig1, tmax1);
-        }
-    };
-    if (sc.lds_bvh) walk(std::true_type{});
-    else walk(std::false_type{});
-    o0 = best0;
-    o1 = best1;
-}
-
-/* trace_any2_uni for N rays per lane (AMVPT_VIS_RAYS = N > 2 in k_vis): the wave enters a node when any lane's
- * ray of any of its N hits its box -- N times the rays in flight per wave on the latency-bound walk */
-template <int kSph, int N>
-AD void trace_anyN_uni(const SceneRef &sc, const Ray *r, const bool *act, bool *f) {
-    BoxRay b[N];
-#pragma unroll
-    for (int h = 0; h < N; ++h) { b[h] = box_ray(r[h]); f[h] = !act[h]; f[h] = f[h] || outer_any(sc, r[h], f[h]); }
-    const uint32_t nn = ufirst(sc.n_nodes);
-    uint32_t node = 0;
-    uint64_t dm = 0;   /* kSph = 2: deferred spheres */
-    auto open = [&]() {
-        bool o = false;
-#pragma unroll
-        for (int h = 0; h < N; ++h) o = o || !f[h];
-        return o;
-    };
-    while (node < nn) {
-        const DNode n = load_uniform(sc.gnodes, node);
-        bool hit = false;
-#pragma unroll
-        for (int h = 0; h < N; ++h) hit = hit || (!f[h] && box_hit(n, b[h], r[h].maxt));
-        const bool enter = wave_any(hit);
-        const uint32_t skc = ufirst(n.skip_count);
-        const uint32_t count = skc >> kNodeCountShift, skip = skc & kNodeSkipMask;
-        if (enter && count) {
-            const uint32_t first = ufirst(n.first);
-            for (uint32_t i = 0; i < count; ++i) {
-                const DPrim p = load_uniform(sc.gprims, first + i);
-                const uint32_t type = ufirst(p.type);
-                if (kSph == 2 && type == PRIM_SPHERE) {
-                    bool m = false;
-#pragma unroll
-                    for (int h = 0; h < N; ++h) m = m || (!f[h] && sphere_maybe(p, r[h]));
-                    if (wave_any(m)) dm |= 1ull << ufirst(p.face);
-                    continue;
-                }
-#pragma unroll
-                for (int h = 0; h < N; ++h) {
-                    float t, u, v;
-                    const bool hh = prim_hit_u<kSph>(p, type, r[h], t, u, v);
-                    f[h] = f[h] || hh;
-                }
-            }
-            if (!wave_any(open())) break;
-        }
-        node = (enter && !count) ? node + 1 : skip;
-    }
-    if constexpr (kSph == 2) {
-        while (dm && wave_any(open())) {
-            const DPrim p = deferred_sphere(sc, mask_pop(dm));
-#pragma unroll
-            for (int h = 0; h < N; ++h) {
-                float t;
-                const bool hh = !f[h] && sphere_hit(p, r[h], t);
-                f[h] = f[h] || hh;
-            }
-        }
-    }
-#pragma unroll
-    for (int h = 0; h < N; ++h) f[h] = f[h] && act[h];
 }
 
 /*
@@ -1329,44 +791,6 @@ template <bool kSph> AD void brute_test(const DPrim &p, uint32_t pi, const Ray &
             best_orig = orig;
         }
     }
-}
-#ifndef AMVPT_PAIR_PRIMS
-/* 1: the brute-force walks test two same-type primitives as one packed pair -- off: at the fused suffix's
- * 80-VGPR budget the pairs spill (240 B of scratch, k_suffix_fused<true, true, 3>) */
-#define AMVPT_PAIR_PRIMS 0
-#endif
-/* the pair (a, b) = primitives (pi, pi + 1): one packed test when both are rectangles or both triangles */
-template <bool kSph> AD void brute_pair(const DPrim &a, const DPrim &b, uint32_t pi, const Ray &ray, Hit &best,
-                                        uint32_t &best_orig) {
-    const uint32_t ta = ufirst(a.type), tb = ufirst(b.type);
-    if (AMVPT_PAIR_PRIMS && ta == tb && ta != PRIM_SPHERE) {
-        Hit2 h;
-        if (ta == PRIM_RECT) h = rect_hit2(prim_pair(a, b), ray_pair(ray));
-        else h = tri_hit2(prim_pair(a, b), ray_pair(ray));
-        const uint32_t orig[2] = {ufirst(a.pad), ufirst(b.pad)};
-#pragma unroll
-        for (int e = 0; e < 2; ++e)
-            if (h.h[e] && (h.t[e] < best.t || (h.t[e] == best.t && orig[e] < best_orig))) {
-                best.t = h.t[e]; best.u = h.u[e]; best.v = h.v[e]; best.prim = (int32_t) (pi + e);
-                best_orig = orig[e];
-            }
-    } else {
-        brute_test<kSph>(a, pi, ray, best, best_orig);
-        brute_test<kSph>(b, pi + 1, ray, best, best_orig);
-    }
-}
-template <bool kSph> AD bool brute_pair_any(const DPrim &a, const DPrim &b, const Ray &ray) {
-    const uint32_t ta = ufirst(a.type), tb = ufirst(b.type);
-    if (AMVPT_PAIR_PRIMS && ta == tb && ta != PRIM_SPHERE) {
-        Hit2 h;
-        if (ta == PRIM_RECT) h = rect_hit2(prim_pair(a, b), ray_pair(ray));
-        else h = tri_hit2(prim_pair(a, b), ray_pair(ray));
-        return h.h[0] || h.h[1];
-    }
-    float t, u, v;
-    const bool ha = prim_hit_b<kSph>(a, ta, ray, t, u, v);
-    const bool hb = prim_hit_b<kSph>(b, tb, ray, t, u, v);
-    return ha || hb;
 }
 /*
  * Box meshes in the brute-force walks (the fused suffix's instruction count).  A `cube` is 12
@@ -1491,7 +915,7 @@ AD void box_walk(const SceneRef &sc, const Ray &ray, Hit &best, uint32_t &best_o
 /* Two records in flight (a, b), each reloaded in place right after its own test: the next
  * record's scalar load overlaps the current test and no record is copied between registers
  * (a one-record prefetch made the compiler move all 16 SGPRs of the record every iteration). */
-/* kSph with AMVPT_SPHERE_DEFER: the float64 sphere tests run after the loop over the primitives (a brute-force
+/* kSph: the float64 sphere tests run after the loop over the primitives (a brute-force
  * scene has <= kBrutePrims < 64 spheres), so the loop allocates like a sphere-free one (see prim_hit_u) */
 template <bool kSph> AD Hit brute_closest(const SceneRef &sc, const Ray &ray) {
     Hit best{kInf, 0.f, 0.f, -1};
@@ -1536,7 +960,7 @@ template <bool kSph> AD Hit brute_closest(const SceneRef &sc, const Ray &ray) {
         }
         return best;
     }
-    constexpr bool kDefer = kSph && AMVPT_SPHERE_DEFER && !AMVPT_PAIR_PRIMS;
+    constexpr bool kDefer = kSph;
     uint64_t dm = 0;
     auto test = [&](const DPrim &p, uint32_t pi) {
         if (ufirst(p.type) == PRIM_SPHERE) {
@@ -1551,12 +975,6 @@ template <bool kSph> AD Hit brute_closest(const SceneRef &sc, const Ray &ray) {
     for (uint32_t pi = 0; pi < np; pi += 2) {
         /* unconditional reloads (index clamped to the table): a conditional one would merge two
          * values of the record and cost a register copy per primitive */
-        if (AMVPT_PAIR_PRIMS && pi + 1 < np) {
-            brute_pair<kSph>(a, b, pi, ray, best, best_orig);
-            a = load_uniform(sc.gprims, min(pi + 2u, last));
-            b = load_uniform(sc.gprims, min(pi + 3u, last));
-            continue;
-        }
         if constexpr (kDefer) {
             test(a, pi);
             a = load_uniform(sc.gprims, min(pi + 2u, last));
@@ -1597,7 +1015,7 @@ template <bool kSph> AD bool brute_any(const SceneRef &sc, const Ray &ray, bool 
             /* a rectangle the wave's open segments certainly do not cross is skipped (rect_plane_miss: its plane
              * lies behind every origin or beyond every segment's end) -- the NEE segments of a closed room stay
              * inside it, so its walls drop out; the exact test otherwise */
-            if (AMVPT_RECT_CULL && !wave_any(!found && !rect_plane_miss(p, ray))) return;
+            if (!wave_any(!found && !rect_plane_miss(p, ray))) return;
             float t, u, v;
             const bool h = rect_hit(p, ray, t, u, v);
             found = found || h;
@@ -1623,7 +1041,7 @@ template <bool kSph> AD bool brute_any(const SceneRef &sc, const Ray &ray, bool 
         }
         return found;
     }
-    constexpr bool kDefer = kSph && AMVPT_SPHERE_DEFER && !AMVPT_PAIR_PRIMS;
+    constexpr bool kDefer = kSph;
     uint64_t dm = 0;
     auto test = [&](const DPrim &p) {
         const uint32_t type = ufirst(p.type);
@@ -1639,12 +1057,7 @@ template <bool kSph> AD bool brute_any(const SceneRef &sc, const Ray &ray, bool 
     DPrim a = load_uniform(sc.gprims, 0), b = load_uniform(sc.gprims, min(1u, last));
     for (uint32_t pi = 0; pi < np; pi += 2) {
         /* branch-free: every lane tests (the wave runs the test anyway while any lane is open) */
-        if (AMVPT_PAIR_PRIMS && pi + 1 < np) {
-            const bool hab = brute_pair_any<kSph>(a, b, ray);
-            found = found || hab;
-            a = load_uniform(sc.gprims, min(pi + 2u, last));
-            b = load_uniform(sc.gprims, min(pi + 3u, last));
-        } else if constexpr (kDefer) {
+        if constexpr (kDefer) {
             test(a);
             a = load_uniform(sc.gprims, min(pi + 2u, last));
             if (pi + 1 < np) test(b);

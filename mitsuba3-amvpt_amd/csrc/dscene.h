@@ -48,7 +48,7 @@ struct alignas(16) DNode2 {
 };
 constexpr uint32_t kRef2Leaf = 0x80000000u, kRef2FirstMask = 0x07ffffffu, kRef2CountShift = 27;
 /*
- * The same node in 32 B (AMVPT_BVH2_HALF): the two child boxes as float16 in the scene's normalized frame
+ * The same node in 32 B (the form the walks read, dgeom.h node2_step): the two child boxes as float16 in the scene's normalized frame
  * (x' = (x - n2_center) * n2_scale, the BVH root box mapped into [-1, 1]^3), each plane rounded outward (lo down, hi
  * up) from the padded float box, so every box contains its float box: a cull test only, never a hit, so the walk
  * finds the same hits.  h[0..5] = (lo0.xy), (lo0.z, hi0.x), (hi0.yz), (lo1.xy), (lo1.z, hi1.x), (hi1.yz), two halves
@@ -152,16 +152,6 @@ struct DScene {
     uint32_t n_bsdfs;
     uint32_t tab_bytes;     /* shapes+bsdfs+emitters footprint if <= kTabBytes (staged in LDS), else 0 */
     uint32_t oct_stride;    /* != 0: nodes[] holds 8 direction-octant orderings of n_nodes each (amvpt_capi.cpp) */
-    /* LDS treelets of large BVHs (the walks stage them per block, dgeom.h trace_*_tl): the nodes of depth
-     * < treelet_depth of each node ordering in depth-first order with treelet-local skip links; a node whose
-     * children lie below the cut is a portal (count 0, first = kPortal | its index in `nodes`), where the walk
-     * continues in the global copy.  t_stride nodes per ordering (1 or 8 of them, as oct_stride); 0: none */
-    const DNode *tnodes;
-    uint32_t t_stride;
-    /* the same for the 8 direction-octant orderings (closest-hit walks, trace_closest_tl): o_stride nodes
-     * each, a shallower cut (all 8 are staged together); 0: none */
-    const DNode *onodes;
-    uint32_t o_stride;
     /* the spheres' primitive indices in scene order of their ordinals (a sphere record's `face` field holds its
      * ordinal): the wave-uniform walks' deferred sphere tests (dgeom.h, kSph = 2) */
     const uint32_t *sph_prims;
@@ -178,13 +168,12 @@ struct DScene {
     const DPrim *outer;
     uint32_t n_outer;
     /* the two-box BVH of the per-lane suffix walks (DNode2; nodes2[0] is the root); n_nodes2 = 0: none (small or
-     * LDS-staged BVHs, a tree deeper than kStack2, or AMVPT_BVH2 off) */
+     * LDS-staged BVHs, or a tree deeper than kStack2) */
     const DNode2 *nodes2;
     uint32_t n_nodes2;
-    const DNode2h *nodes2h;       /* the float16 form of nodes2 (AMVPT_BVH2_HALF), in the normalized frame: */
+    const DNode2h *nodes2h;       /* the float16 form of nodes2, what the walks read, in the normalized frame: */
     float n2_center[3], n2_scale; /*   x' = (x - n2_center) * n2_scale */
 };
 constexpr uint32_t kOuterMax = 8;
-constexpr uint32_t kPortal = 0x80000000u;
 
 } // namespace amvpt

@@ -1,7 +1,7 @@
 """Timed Msamples/s of config M (or $AB_CONFIG) for each variant: a library dir or an environment setting.
 
     python tools/ab_value.py <libdir> [<libdir> ...]    (dirs relative to mitsuba3-amvpt_amd/)
-    python tools/ab_value.py --env AMVPT_BRUTE=0 --env AMVPT_BRUTE=1 ...   (current lib/)
+    python tools/ab_value.py --env AB_FLAGS=0 --env AB_FLAGS=32 ...   (current lib/; AB_FLAGS: amvpt_render_opts.flags)
 Each variant runs in its own child process (one ctypes load per process).  With --kernels
 the child also reports one instrumented frame's per-kernel HIP-event ms (ABI >= 4 only).
 """
