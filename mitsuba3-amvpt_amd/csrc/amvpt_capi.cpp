@@ -719,7 +719,9 @@ amvpt_status amvpt_scene_create(const amvpt_scene_desc *d, amvpt_scene **out) {
          * their ray's direction octant: nearest child first, so the closest hit shrinks the
          * box-test range early */
         const uint32_t n0 = (uint32_t) nodes.size();
-        const uint64_t lds_b = (uint64_t) n0 * sizeof(DNode) + bprims.size() * sizeof(DPrim);
+        /* the bytes the LDS-staged tier copies (DScene::lds_bytes below: the outer rectangles follow the BVH's
+         * primitives in prims[]), so a BVH is staged or gets the copies and the two-box tree, never neither */
+        const uint64_t lds_b = (uint64_t) n0 * sizeof(DNode) + (bprims.size() + outer_idx.size()) * sizeof(DPrim);
         if (n0 > kUniformNodeLimit && lds_b > kLdsSceneBytes && (uint64_t) n0 * 8 <= kNodeSkipMask) {
             nodes.reserve((size_t) n0 * 8);
             for (uint32_t o = 1; o < 8; ++o) b.flatten(0, nodes, o, o * n0);
