@@ -143,16 +143,21 @@ def set_run_exchange(fn):
     lib().oracle_set_run_exchange(_run_exchange_cb, None)
 
 
-def render_rect(scene_desc_ptr, views_ptr, params, rect, threads=0, film=None):
-    """Render the lanes of quilt pixels rect = (x0, y0, width, height) into a whole-quilt film."""
+def render_rect(scene_desc_ptr, views_ptr, params, rect, threads=0, film=None, fixed_film=False):
+    """Render the lanes of quilt pixels rect = (x0, y0, width, height) into a whole-quilt film.
+    fixed_film: as in render()."""
     L = lib()
     C = 5 if params.film_alpha else 4
     if film is None:
         film = np.zeros((params.film_height, params.film_width, C), dtype=np.float32)
     st = OracleStats()
-    rc = L.oracle_render_rect(ctypes.cast(scene_desc_ptr, ctypes.c_void_p), ctypes.cast(views_ptr, ctypes.c_void_p),
-                              ctypes.addressof(params), *[int(v) for v in rect], film.ctypes.data, threads,
-                              ctypes.byref(st))
+    L.oracle_set_fixed_film(1 if fixed_film else 0)
+    try:
+        rc = L.oracle_render_rect(ctypes.cast(scene_desc_ptr, ctypes.c_void_p),
+                                  ctypes.cast(views_ptr, ctypes.c_void_p), ctypes.addressof(params),
+                                  *[int(v) for v in rect], film.ctypes.data, threads, ctypes.byref(st))
+    finally:
+        L.oracle_set_fixed_film(0)
     if rc != 0:
         raise RuntimeError("oracle_render_rect failed (status %d)" % rc)
     return film, st.as_dict()
