@@ -104,6 +104,14 @@ class FilmWindow(ctypes.Structure):
                 ("overflow", ctypes.c_void_p), ("overflow_capacity", u64)]
 
 
+class FixedWindow(ctypes.Structure):
+    """amvpt_fixed_window (include/amvpt_fixed.h): FilmWindow in integers -- a device int64 film of 32.32
+    fixed-point sums, plus the overflow list (16-B header with the u64 entry count, then 16-B entries
+    {u64 quilt float index, i64 value}) for cells outside."""
+    _fields_ = [("film", ctypes.c_void_p), ("x0", u32), ("y0", u32), ("width", u32), ("height", u32),
+                ("overflow", ctypes.c_void_p), ("overflow_capacity", u64)]
+
+
 # amvpt_run_exchange_fn: (ctx, n_runs, *run_lane_begin, *run_count, *run_prefix, *total) -> 0 on success
 RunExchangeFn = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, u32, ctypes.POINTER(u64), ctypes.POINTER(u64),
                                  ctypes.POINTER(u64), ctypes.POINTER(u64))
@@ -124,6 +132,7 @@ OPT_NO_BOX_SCREEN = 64
 OPT_THREADED_BVH = 128
 OPT_SPLIT_PRIMARY = 256
 OPT_BLOCK_SPLAT = 512   # ABI 12: the per-lane block-window splat even where the row-reduced one is eligible
+OPT_FIXED_DIRECT = 1024  # amvpt_fixed.h: direct puts into the fixed-point film instead of the integer LDS window
 
 # amvpt_params.rfilter
 RFILTER_BOX, RFILTER_GAUSSIAN, RFILTER_TENT, RFILTER_MITCHELL, RFILTER_CATMULLROM, RFILTER_LANCZOS = range(6)
@@ -200,8 +209,77 @@ def hip_lib():
             L.amvpt_rfilter_eval.restype = ctypes.c_int
             L.amvpt_rfilter_eval.argtypes = [ctypes.POINTER(Params), ctypes.c_void_p, u32, ctypes.c_void_p,
                                              ctypes.POINTER(f32)]
+        if hasattr(L, "amvpt_fixed_version"):   # include/amvpt_fixed.h
+            L.amvpt_fixed_version.restype = u32
+            for fn in ("amvpt_render_fixed", "amvpt_fixed_accumulate", "amvpt_fixed_resolve",
+                       "amvpt_fixed_accumulate_host", "amvpt_fixed_resolve_host"):
+                getattr(L, fn).restype = ctypes.c_int
+            L.amvpt_render_fixed.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(Params),
+                                             ctypes.POINTER(LaneSet), ctypes.POINTER(FixedWindow), ctypes.c_void_p,
+                                             ctypes.POINTER(RenderOpts), ctypes.POINTER(Counters)]
+            acc = [ctypes.c_void_p, u32, u32, u32, ctypes.c_void_p, u32, u32, u32, u32, ctypes.c_void_p, u64]
+            L.amvpt_fixed_accumulate.argtypes = acc + [ctypes.c_void_p]
+            L.amvpt_fixed_accumulate_host.argtypes = acc
+            L.amvpt_fixed_resolve.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u64, ctypes.c_int, ctypes.c_void_p]
+            L.amvpt_fixed_resolve_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u64, ctypes.c_int]
         _hip = L
     return _hip
+
+
+def fixed_version():
+    """AMVPT_FIXED_VERSION of the loaded library (include/amvpt_fixed.h)."""
+    return hip_lib().amvpt_fixed_version()
+
+
+def fixed_accumulate(quilt_ptr, quilt_width, quilt_height, channels, window_ptr, window, entries_ptr=None,
+                     n_entries=0, stream=None):
+    """amvpt_fixed_accumulate: the int64 quilt (device) += the int64 window (x0, y0, width, height) and the
+    `n_entries` 16-byte overflow entries at `entries_ptr` (the entries after a list's header)."""
+    L = hip_lib()
+    x0, y0, w, h = window
+    _check(L.amvpt_fixed_accumulate(ctypes.c_void_p(quilt_ptr), quilt_width, quilt_height, channels,
+                                    ctypes.c_void_p(window_ptr or 0), x0, y0, w, h,
+                                    ctypes.c_void_p(entries_ptr or 0), n_entries, ctypes.c_void_p(stream)), L)
+
+
+def fixed_accumulate_host(quilt, window_film, window, entries=None):
+    """amvpt_fixed_accumulate_host over numpy arrays: `quilt` (H, W, C) int64, C-contiguous, updated in place;
+    `window_film` (h, w, C) int64 or None; `window` (x0, y0, w, h); `entries` (n, 2) int64 (index, value) or None."""
+    L = hip_lib()
+    if quilt.dtype != np.int64 or not quilt.flags.c_contiguous or quilt.ndim != 3:
+        raise ValueError("fixed_accumulate_host: quilt must be a C-contiguous (H, W, C) int64 array")
+    x0, y0, w, h = window
+    win = None if window_film is None else np.ascontiguousarray(window_film, dtype=np.int64)
+    if win is not None and win.shape != (h, w, quilt.shape[2]):
+        raise ValueError("fixed_accumulate_host: window_film is not (h, w, C) of `window`")
+    ent = None if entries is None else np.ascontiguousarray(entries, dtype=np.int64).reshape(-1, 2)
+    _check(L.amvpt_fixed_accumulate_host(quilt.ctypes.data, quilt.shape[1], quilt.shape[0], quilt.shape[2],
+                                         win.ctypes.data if win is not None else None, x0, y0, w, h,
+                                         ent.ctypes.data if ent is not None and len(ent) else None,
+                                         len(ent) if ent is not None else 0), L)
+    return quilt
+
+
+def fixed_resolve(fixed_ptr, film_ptr, n_floats, add=False, stream=None):
+    """amvpt_fixed_resolve: film[i] (float32, device) = or += (float) ((double) fixed[i] * 2^-32)."""
+    L = hip_lib()
+    _check(L.amvpt_fixed_resolve(ctypes.c_void_p(fixed_ptr), ctypes.c_void_p(film_ptr), n_floats, int(bool(add)),
+                                 ctypes.c_void_p(stream)), L)
+
+
+def fixed_resolve_host(fixed, film=None, add=False):
+    """amvpt_fixed_resolve_host over numpy arrays: the float32 film of the int64 array `fixed` (same shape);
+    with `add`, `film` (float32, C-contiguous) is added to in place."""
+    L = hip_lib()
+    fx = np.ascontiguousarray(fixed, dtype=np.int64)
+    if film is None:
+        if add:
+            raise ValueError("fixed_resolve_host: add needs a film")
+        film = np.empty(fx.shape, dtype=np.float32)
+    if film.dtype != np.float32 or not film.flags.c_contiguous or film.size != fx.size:
+        raise ValueError("fixed_resolve_host: film must be a C-contiguous float32 array of fixed's size")
+    _check(L.amvpt_fixed_resolve_host(fx.ctypes.data, film.ctypes.data, fx.size, int(bool(add))), L)
+    return film
 
 
 def host_lib():
@@ -545,6 +623,26 @@ class DeviceScene:
         _check(self._lib.amvpt_render_ex(self.h, views_ptr, ctypes.byref(params), ctypes.byref(lanes),
                                          ctypes.byref(fw), ctypes.c_void_p(stream), ctypes.byref(o),
                                          ctypes.byref(counters) if counters is not None else None), self._lib)
+        return counters
+
+    def render_fixed(self, views_ptr, params, fixed_ptr, lanes=None, window=None, overflow_ptr=None,
+                     overflow_capacity=0, stream=None, counters=None, chunk_lanes=None, traversal=None, flags=0,
+                     exchange=None, records_ptr=None, record_pass=0, budget_mib=0):
+        """amvpt_render_fixed: render_ex into the caller's int64 fixed-point window at `fixed_ptr` (accumulated
+        into: neither cleared nor resolved) with an int64 overflow list (2 header words, 2 words per entry)."""
+        if lanes is None:
+            lanes = LaneSet(0, 2 ** 64 - 1, 0, 0, 0, 0)
+        chunk_lanes = _DEFAULTS["chunk_lanes"] if chunk_lanes is None else chunk_lanes
+        traversal = _DEFAULTS["traversal"] if traversal is None else traversal
+        x0, y0, w, h = window if window is not None else (0, 0, params.film_width, params.film_height)
+        fw = FixedWindow(ctypes.c_void_p(fixed_ptr), x0, y0, w, h, ctypes.c_void_p(overflow_ptr or 0),
+                         overflow_capacity)
+        cb = wrap_run_exchange(exchange) if exchange is not None else RunExchangeFn()
+        o = RenderOpts(chunk_lanes, traversal, flags, cb, None, ctypes.c_void_p(records_ptr or 0), record_pass,
+                       int(budget_mib))
+        _check(self._lib.amvpt_render_fixed(self.h, views_ptr, ctypes.byref(params), ctypes.byref(lanes),
+                                            ctypes.byref(fw), ctypes.c_void_p(stream), ctypes.byref(o),
+                                            ctypes.byref(counters) if counters is not None else None), self._lib)
         return counters
 
     def render_records(self, views_ptr, params, film_ptr, records_ptr, pass_index=0, lane_begin=0,

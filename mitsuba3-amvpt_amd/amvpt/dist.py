@@ -310,3 +310,105 @@ def gather_windows(window_film, window, overflow, quilt, windows, dst=0):
             if counts[r]:
                 flat.index_add_(0, recv[r][1].to(quilt.device), recv[r][2].to(quilt.device))
     return quilt
+
+
+# ---------------------------------------------------------------------------------------------------
+# The fixed-point film (include/amvpt_fixed.h): exact frames across ranks
+# ---------------------------------------------------------------------------------------------------
+# A rank zeroes an int64 window, calls DeviceScene.render_fixed on its lane set, the ranks' integers are summed
+# with reduce_fixed (lane bands) or gather_fixed_windows (view groups), and rank 0 calls amvpt.fixed_resolve once.
+# Integer sums do not depend on their grouping, so the frame is the single-device frame bit for bit.
+
+def reduce_fixed(fixed, dst=0):
+    """Sum the ranks' int64 fixed-point films on `dst` (an integer SUM reduce: exact; under gloo a GPU film goes
+    through the host, comm_device)."""
+    import torch
+    import torch.distributed as dist
+    if fixed.dtype != torch.int64:
+        raise ValueError("reduce_fixed: the fixed-point film is an int64 tensor")
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        if fixed.is_cuda and comm_device(fixed.device) == "cpu":
+            t = fixed.cpu()
+            dist.reduce(t, dst=dst, op=dist.ReduceOp.SUM)
+            if dist.get_rank() == dst:
+                fixed.copy_(t)
+        else:
+            dist.reduce(fixed, dst=dst, op=dist.ReduceOp.SUM)
+    return fixed
+
+
+def fixed_overflow_entries(overflow):
+    """The (n, 2) int64 entries (quilt float index, 32.32 value) of a fixed-point overflow list (int64 tensor:
+    2 header words, then 2 words per entry), a view of the list on its device."""
+    cnt = int(overflow[0].item())
+    cap = overflow.numel() // 2 - 1
+    if cnt > cap:
+        raise RuntimeError("fixed overflow list full: %d > %d" % (cnt, cap))
+    return overflow[2:2 + 2 * cnt].view(cnt, 2)
+
+
+def _fixed_accumulate(quilt, window, rect, entries):
+    """quilt (H, W, C) int64 += window at rect, += entries: amvpt_fixed_accumulate on a GPU quilt, its host twin
+    on a CPU one."""
+    import amvpt
+    H, W, C = quilt.shape
+    window = window.to(quilt.device).contiguous()
+    entries = entries.to(quilt.device).contiguous()
+    if quilt.is_cuda:
+        amvpt.fixed_accumulate(quilt.data_ptr(), W, H, C, window.data_ptr(), rect,
+                               entries.data_ptr() if entries.numel() else None, entries.shape[0])
+    else:
+        amvpt.fixed_accumulate_host(quilt.numpy(), window.numpy(), rect, entries.numpy())
+
+
+def gather_fixed_windows(window, rect, overflow, quilt, windows, dst=0):
+    """gather_windows in integers: assemble the whole-quilt fixed-point film on `dst` from every rank's int64
+    `window` (this rank's quilt rectangle `rect`; borders overlap: summed) and fixed overflow list.  `windows`
+    lists every rank's (x0, y0, w, h); `quilt` (H, W, C) int64, contiguous, is written on dst only (zeroed
+    first).  Point-to-point sends to dst; a single process just adds its own."""
+    import torch
+    import torch.distributed as dist
+    multi = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+    rank = dist.get_rank() if multi else 0
+    world = dist.get_world_size() if multi else 1
+    if multi and tuple(windows[rank]) != tuple(rect):
+        raise ValueError("gather_fixed_windows: rect is not this rank's entry of windows")
+    ent = fixed_overflow_entries(overflow)
+    dev = comm_device(window.device) if multi else window.device   # gloo: through the host
+    if multi:
+        n = torch.tensor([ent.shape[0]], dtype=torch.int64, device=dev)
+        ns = [torch.zeros_like(n) for _ in range(world)]
+        dist.all_gather(ns, n)
+        counts = [int(x.item()) for x in ns]
+    else:
+        counts = [ent.shape[0]]
+    if rank != dst:
+        ops = [dist.P2POp(dist.isend, window.contiguous().to(dev), dst)]
+        if counts[rank]:
+            ops.append(dist.P2POp(dist.isend, ent.contiguous().to(dev), dst))
+        for w in dist.batch_isend_irecv(ops):
+            w.wait()
+        return None
+    C = quilt.shape[2]
+    quilt.zero_()
+    recv = {}
+    ops = []
+    for r in range(world):
+        if r == rank:
+            continue
+        x0, y0, w, h = windows[r]
+        t = torch.empty((h, w, C), dtype=torch.int64, device=dev)
+        e = torch.empty((counts[r], 2), dtype=torch.int64, device=dev)
+        recv[r] = (t, e)
+        ops.append(dist.P2POp(dist.irecv, t, r))
+        if counts[r]:
+            ops.append(dist.P2POp(dist.irecv, e, r))
+    if ops:
+        for w in dist.batch_isend_irecv(ops):
+            w.wait()
+    for r in range(world):
+        if r == rank:
+            _fixed_accumulate(quilt, window, tuple(rect), ent)
+        else:
+            _fixed_accumulate(quilt, recv[r][0], tuple(windows[r]), recv[r][1])
+    return quilt

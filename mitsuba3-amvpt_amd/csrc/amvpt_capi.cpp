@@ -1055,6 +1055,35 @@ amvpt_status amvpt_render_ex(amvpt_scene *scene, const amvpt_view_desc *views, c
     return render_impl(scene, views, params, *lanes, *film, stream, o, counters, o.records, o.record_pass);
 }
 
+amvpt_status amvpt_render_fixed(amvpt_scene *scene, const amvpt_view_desc *views, const amvpt_params *params,
+                                const amvpt_lane_set *lanes, const amvpt_fixed_window *film, void *stream,
+                                const amvpt_render_opts *opts, amvpt_counters *counters) {
+    if (!lanes || !film) { set_error("amvpt_render_fixed: null lane set or fixed window"); return AMVPT_ERR_INVALID; }
+    if (!device_ok()) { set_error("amvpt_render_fixed: no HIP device visible"); return AMVPT_ERR_NO_DEVICE; }
+    const amvpt_render_opts defaults{};
+    const amvpt_render_opts &o = opts ? *opts : defaults;
+    /* the integer window and list travel in a film window's fields (render_impl's fixed_film) */
+    amvpt_film_window w{};
+    w.film = reinterpret_cast<float *>(film->film);
+    w.x0 = film->x0; w.y0 = film->y0; w.width = film->width; w.height = film->height;
+    w.overflow = reinterpret_cast<uint32_t *>(film->overflow);
+    w.overflow_capacity = film->overflow_capacity;
+    return render_impl(scene, views, params, *lanes, w, stream, o, counters, o.records, o.record_pass, true);
+}
+
+amvpt_status amvpt_fixed_accumulate(int64_t *quilt, uint32_t quilt_width, uint32_t quilt_height, uint32_t channels,
+                                    const int64_t *window, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height,
+                                    const uint64_t *overflow_entries, uint64_t n_entries, void *stream) {
+    if (!device_ok()) { set_error("amvpt_fixed_accumulate: no HIP device visible"); return AMVPT_ERR_NO_DEVICE; }
+    return fixed_accumulate_impl(quilt, quilt_width, quilt_height, channels, window, x0, y0, width, height,
+                                 overflow_entries, n_entries, stream);
+}
+
+amvpt_status amvpt_fixed_resolve(const int64_t *fixed, float *film, uint64_t n_floats, int add, void *stream) {
+    if (!device_ok()) { set_error("amvpt_fixed_resolve: no HIP device visible"); return AMVPT_ERR_NO_DEVICE; }
+    return fixed_resolve_impl(fixed, film, n_floats, add, stream);
+}
+
 amvpt_status amvpt_film_accumulate(float *quilt, uint32_t quilt_width, uint32_t quilt_height, uint32_t channels,
                                    const float *window, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height,
                                    const uint32_t *overflow_entries, uint64_t n_entries, void *stream) {

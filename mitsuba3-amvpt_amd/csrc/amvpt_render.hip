@@ -34,6 +34,7 @@
 
 #include "internal.h"   /* the C-ABI enums (amvpt.h) before the device headers use them */
 #include "dbsdf.h"
+#include "dfixed.h"
 
 /* non-template kernels get internal linkage in the k_shadow translation unit (amvpt_shadow.hip) */
 #if defined(AMVPT_SHADOW_TU) || defined(AMVPT_GROUP_TU)
@@ -253,6 +254,7 @@ struct KParams {
     uint32_t split_prim;  /* host only (launch_primary): AMVPT_OPT_SPLIT_PRIMARY, no fused primary vertex */
     float bin_lo[3], bin_scale[3];   /* ray binning: the scene box's low corner and cells per unit (bin_key) */
     uint32_t filt_kind;   /* FILT_* of `filt` (dmath.h): what the FK_ANY splat instances evaluate */
+    uint32_t fx_direct;   /* film_fx set: direct puts (AMVPT_OPT_FIXED_DIRECT) instead of the integer LDS window */
 };
 
 /* the PCG32 a stock-path lane starts the pass with: TEA-seeded, or the previous pass's state (same
@@ -805,14 +807,20 @@ AD f3 camera_point(const DView &v, float apx, float apy) {
  */
 constexpr double kFixScale = 4294967296.0, kFixLimit = 2147483647.0;
 /* kDet = false: a kernel instance that never runs in deterministic mode (the row splat) */
+/* one cell add as 32.32 fixed point: false when the add is dropped (non-finite, or out of range and counted) */
+AD bool fix_convert(const KParams &P, float v, unsigned long long &q) {
+    const double d = (double) v * kFixScale;
+    if (!(fabs(d) < kFixLimit * kFixScale)) {   /* NaN / Inf (counted per sample by check_sample) / out of range */
+        if (P.fx_drops && __builtin_isfinite(v)) atomicAdd(P.fx_drops + blockIdx.x % 256u, 1ull);   /* kStatShards */
+        return false;
+    }
+    q = (unsigned long long) (long long) __builtin_rint(d);
+    return true;
+}
 template <bool kDet = true> AD void film_add(const KParams &P, float *p, float v) {
     if (kDet && P.film_fx) {
-        const double d = (double) v * kFixScale;
-        if (!(fabs(d) < kFixLimit * kFixScale)) {   /* NaN / Inf (counted per sample by check_sample) / out of range */
-            if (P.fx_drops && __builtin_isfinite(v)) atomicAdd(P.fx_drops + blockIdx.x % 256u, 1ull);   /* kStatShards */
-            return;
-        }
-        atomicAdd(P.film_fx + (p - P.film_base), (unsigned long long) (long long) __builtin_rint(d));
+        unsigned long long q;
+        if (fix_convert(P, v, q)) atomicAdd(P.film_fx + (p - P.film_base), q);
         return;
     }
     atomicAdd(p, v);
@@ -843,8 +851,25 @@ AD void overflow_push(const KParams &P, uint64_t idx, float v) {
     if (e < P.ov_cap)
         reinterpret_cast<uint4 *>(P.overflow + 4)[e] = make_uint4((uint32_t) idx, (uint32_t) (idx >> 32), __float_as_uint(v), 0u);
 }
+/* the fixed-point film's list (amvpt_fixed_window): the same header, 16-B entries {u64 quilt float index, i64 value} */
+AD void overflow_push_fx(const KParams &P, uint64_t idx, unsigned long long q) {
+    if (!P.overflow) return;
+    const unsigned long long e = atomicAdd(reinterpret_cast<unsigned long long *>(P.overflow), 1ull);
+    if (e < P.ov_cap)
+        reinterpret_cast<uint4 *>(P.overflow + 4)[e] = make_uint4((uint32_t) idx, (uint32_t) (idx >> 32), (uint32_t) q, (uint32_t) (q >> 32));
+}
+/* one converted add of quilt cell (x, y), channel k: the fixed-point window, else its overflow list */
+AD void fixed_cell_add(const KParams &P, int x, int y, int k, unsigned long long q) {
+    if (in_window(P, x, y)) atomicAdd(P.film_fx + (film_cell(P, P.film_base, x, y, k) - P.film_base), q);
+    else overflow_push_fx(P, ((uint64_t) (uint32_t) y * P.W + (uint32_t) x) * P.C + (uint32_t) k, q);
+}
 /* one film float of quilt cell (x, y), channel k: the window, else the overflow list */
 template <bool kWin = true, bool kDet = true> AD void film_cell_add(const KParams &P, float *film, int x, int y, int k, float v) {
+    if (kDet && P.film_fx) {
+        unsigned long long q;
+        if (fix_convert(P, v, q)) fixed_cell_add(P, x, y, k, q);
+        return;
+    }
     if (in_window<kWin>(P, x, y)) film_add<kDet>(P, film_cell<kWin>(P, film, x, y, k), v);
     else overflow_push(P, ((uint64_t) (uint32_t) y * P.W + (uint32_t) x) * P.C + (uint32_t) k, v);
 }
@@ -986,6 +1011,13 @@ AD void lds_add64(double *p, double v) {
     (void) __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 AD void win_add(double *p, float x) { lds_add64(p, (double) x); }
+/* the fixed-point window's add: the cell add converted as film_add converts it (range test and drop count per
+ * add, before anything is summed), then one no-return ds_add_u64 into the cell's 8 bytes */
+AD void win_add_fx(const KParams &P, WinT *p, float x) {
+    unsigned long long q;
+    if (fix_convert(P, x, q))
+        (void) __hip_atomic_fetch_add(reinterpret_cast<unsigned long long *>(p), q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
 
 /* The block's window: union of the active footprints, clamped to kWinW x kWinH. */
 struct Win { int bx0, by0, ww, wh, rs, plane; };   /* rs: LDS row stride (cells) >= ww; plane >= rs * wh */
@@ -1035,7 +1067,9 @@ AD Win window_bbox(SplatLds<C> &L, int buf, bool act, int cx0, int cy0, int x1, 
 
 /* barrier, then one global float atomic per touched film float of the window; the window
  * is re-zeroed on the way (consecutive threads take consecutive floats of a film row) */
-template <int C>
+/* kFx: the fixed-point window (KParams::film_fx): the cells are 64-bit integer sums, one global integer atomic per
+ * non-zero cell into the fixed-point film, or its overflow list */
+template <int C, bool kFx = false>
 AD void window_flush(const KParams &P, float *film, SplatLds<C> &L, const Win &w) {
     __syncthreads();
     const int plane = w.plane;
@@ -1056,10 +1090,16 @@ AD void window_flush(const KParams &P, float *film, SplatLds<C> &L, const Win &w
         const WinT d = *src;
         if (__double_as_longlong(d) != 0ll) {
             *src = 0.0;
-            const float v = (float) d;
-            if (v != 0.f || v != v) {
-                if (inside) film_add(P, film0 + (size_t) cy * film_row + r, v);
-                else film_cell_add(P, film, w.bx0 + cx, w.by0 + cy, k, v);
+            if constexpr (kFx) {
+                const unsigned long long q = (unsigned long long) __double_as_longlong(d);
+                if (inside) atomicAdd(P.film_fx + ((film0 - P.film_base) + (size_t) cy * film_row + r), q);
+                else fixed_cell_add(P, w.bx0 + cx, w.by0 + cy, k, q);
+            } else {
+                const float v = (float) d;
+                if (v != 0.f || v != v) {
+                    if (inside) film_add(P, film0 + (size_t) cy * film_row + r, v);
+                    else film_cell_add(P, film, w.bx0 + cx, w.by0 + cy, k, v);
+                }
             }
         }
     }
@@ -1068,7 +1108,8 @@ AD void window_flush(const KParams &P, float *film, SplatLds<C> &L, const Win &w
 /* one footprint's cells straight into the window (or the film when it does not fit) */
 /* kRolled: the window loop is not unrolled (row_put's rare per-lane path: an unrolled 5 x 5 x C
  * body would set the register allocation of the whole splat kernel) */
-template <int C, bool kRolled = false, bool kWin = true, bool kDet = true, int kF = FK_LEGACY>
+/* kFx: the window holds fixed-point sums (win_add_fx); its misses are film_cell_add's fixed-point adds */
+template <int C, bool kRolled = false, bool kWin = true, bool kDet = true, int kF = FK_LEGACY, bool kFx = false>
 AD void foot_add(const KParams &P, float *film, WinT *const wbase, const Win &wn, const Foot &f, const float *wx,
                  const float *wy, const float *vals, bool coalesce, uint32_t *fallback) {
     const int cx0 = max(f.x0, 0), cy0 = max(f.y0, 0);
@@ -1090,7 +1131,10 @@ AD void foot_add(const KParams &P, float *film, WinT *const wbase, const Win &wn
                     const float w = wx[xs] * wy[ys];
                     WinT *const cp = c0 + ys * wn.rs + xs;
 #pragma unroll
-                    for (int k = 0; k < C; ++k) win_add(cp + k * plane, P.box ? vals[k] : vals[k] * w);
+                    for (int k = 0; k < C; ++k) {
+                        if constexpr (kFx) win_add_fx(P, cp + k * plane, P.box ? vals[k] : vals[k] * w);
+                        else win_add(cp + k * plane, P.box ? vals[k] : vals[k] * w);
+                    }
                 }
             }
         }
@@ -1114,9 +1158,10 @@ AD void foot_add(const KParams &P, float *film, WinT *const wbase, const Win &wn
 }
 
 /*
- * Deterministic mode's put: every cell of the sample's footprint straight into the fixed-point film,
- * value * (wx * wy) per cell as ImageBlock::put forms it (imageblock.cpp:265-558) -- no LDS window and
- * no row reduction, so no float sum depends on which lanes share a wave, a chunk or a stream.
+ * The fixed-point film's direct put (AMVPT_OPT_FIXED_DIRECT; until the integer window, block_put<.., kFx>, the only
+ * one): every cell of the sample's footprint straight into the fixed-point film, value * (wx * wy) per cell as
+ * ImageBlock::put forms it (imageblock.cpp:265-558), one global integer atomic each.  The window sums the same
+ * integers in another grouping, so both leave the same film.
  */
 template <int C, bool kWin = true, int kF = FK_LEGACY>
 AD void direct_put(const KParams &P, float *film, float px, float py, const float *vals, bool valid, bool coalesce) {
@@ -1374,7 +1419,7 @@ AD void wave_put(const KParams &P, float *film, WaveLds<C> &L, float px, float p
  * coalesced footprint may start left/above the film).  Weight of a cell =
  * eval(rx + xs) * eval(ry + ys).  `coalesce` is uniform over the block.
  */
-template <int C, int kF = FK_LEGACY>
+template <int C, int kF = FK_LEGACY, bool kFx = false>
 AD void block_put(const KParams &P, float *film, SplatLds<C> &L, int buf, float px, float py, const float *vals,
                   bool valid, bool coalesce, uint32_t *fallback = nullptr) {
     Foot f;
@@ -1385,14 +1430,14 @@ AD void block_put(const KParams &P, float *film, SplatLds<C> &L, int buf, float 
     const Win wn = window_bbox(L, buf, act, max(f.x0, 0), max(f.y0, 0), f.x0 + f.nx, f.y0 + f.ny, (int) P.win_rs,
                                P.row_splat != 0);
     /* (the row-reduced put inside the block window: the default Gaussian's only) */
-    if (kF == FK_LEGACY && C == 4 && P.row_splat) {
-        if constexpr (kF == FK_LEGACY) row_put_win<C>(P, film, L.win, wn, f, act, vals, coalesce, fallback, row_box(f, act));
+    if (!kFx && kF == FK_LEGACY && C == 4 && P.row_splat) {
+        if constexpr (!kFx && kF == FK_LEGACY) row_put_win<C>(P, film, L.win, wn, f, act, vals, coalesce, fallback, row_box(f, act));
     } else if (act) {
         float wx[kMaxFoot], wy[kMaxFoot];
         foot_weights<kF>(P, f, wx, wy);
-        foot_add<C, false, true, true, kF>(P, film, L.win, wn, f, wx, wy, vals, coalesce, fallback);
+        foot_add<C, false, true, true, kF, kFx>(P, film, L.win, wn, f, wx, wy, vals, coalesce, fallback);
     }
-    window_flush<C>(P, film, L, wn);
+    window_flush<C, kFx>(P, film, L, wn);
 }
 
 /*
@@ -2270,7 +2315,8 @@ __global__ void __launch_bounds__(kFusedBlock, kDiff ? AMVPT_FUSED_WAVES : AMVPT
 /* ------------------------------------------------------------------ */
 
 /* kF: the instance's filter form (FK_LEGACY: box / Gaussian; FK_ANY: the other filters, by P.filt_kind) */
-template <int C, int kF = FK_LEGACY>
+/* kFx: the fixed-point film's instance (P.film_fx set: the integer LDS window, or direct puts with P.fx_direct) */
+template <int C, int kF = FK_LEGACY, bool kFx = false>
 __global__ void __launch_bounds__(kSplatBlock) k_splat_single(KParams P, Bufs B) {
     __shared__ SplatLds<C> L;
     splat_lds_init(L);
@@ -2300,12 +2346,16 @@ __global__ void __launch_bounds__(kSplatBlock) k_splat_single(KParams P, Bufs B)
     }
     unsigned long long nonfinite = 0, negative = 0;
     check_sample(P, vals, ok, nonfinite, negative);
-    if (P.film_fx) direct_put<C, true, kF>(P, B.film, putx, puty, vals, ok, P.coalesce_single != 0);
-    else block_put<C, kF>(P, B.film, L, 0, putx, puty, vals, ok, P.coalesce_single != 0);
+    if constexpr (kFx) {
+        if (P.fx_direct) direct_put<C, true, kF>(P, B.film, putx, puty, vals, ok, P.coalesce_single != 0);
+        else block_put<C, kF, true>(P, B.film, L, 0, putx, puty, vals, ok, P.coalesce_single != 0);
+    } else {
+        block_put<C, kF>(P, B.film, L, 0, putx, puty, vals, ok, P.coalesce_single != 0);
+    }
     if (B.stats) { stat_add(B.stats, 6, nonfinite); stat_add(B.stats, 7, negative); }
 }
 
-template <int C, int kF = FK_LEGACY>
+template <int C, int kF = FK_LEGACY, bool kFx = false>
 __global__ void __launch_bounds__(kSplatBlock) k_splat_adapt(KParams P, Bufs B) {
     __shared__ SplatLds<C> L;
     splat_lds_init(L);
@@ -2323,8 +2373,12 @@ __global__ void __launch_bounds__(kSplatBlock) k_splat_adapt(KParams P, Bufs B) 
     }
     unsigned long long nonfinite = 0, negative = 0;
     check_sample(P, vals, ok, nonfinite, negative);
-    if (P.film_fx) direct_put<C, true, kF>(P, B.film, sx, sy, vals, ok, false);
-    else block_put<C, kF>(P, B.film, L, 0, sx, sy, vals, ok, false);
+    if constexpr (kFx) {
+        if (P.fx_direct) direct_put<C, true, kF>(P, B.film, sx, sy, vals, ok, false);
+        else block_put<C, kF, true>(P, B.film, L, 0, sx, sy, vals, ok, false);
+    } else {
+        block_put<C, kF>(P, B.film, L, 0, sx, sy, vals, ok, false);
+    }
     if (B.stats) { stat_add(B.stats, 6, nonfinite); stat_add(B.stats, 7, negative); }
 }
 
@@ -3203,7 +3257,8 @@ __global__ void __launch_bounds__(prim_block<G>(), kFuse ? AMVPT_PRIM_FUSE_WAVES
 /* kF: the instance's filter form (FK_LEGACY: box / Gaussian, the row splat with the default Gaussian's literals;
  * FK_ANY: the other filters on the block window and the direct puts; FK_TENT / FK_MITCHELL / FK_CATMULLROM: their
  * row splat, plain renders only) */
-template <int G, int C, bool kDiff, bool kRow, bool kWin = true, bool kRec = true, int kF = FK_LEGACY>
+/* kFx: the fixed-point film's instance (block window only; launch_splat takes it whenever P.film_fx is set) */
+template <int G, int C, bool kDiff, bool kRow, bool kWin = true, bool kRec = true, int kF = FK_LEGACY, bool kFx = false>
 __global__ void __launch_bounds__(kSplatBlock, AMVPT_SPLAT_WAVES) k_splat_multi(KParams P, const DView *V, Bufs B) {
     const bool rec_ = kRec && P.record != 0, dbg_ = kRec && P.debug != 0;
     __shared__ typename std::conditional<kRow, WaveLds<C>, SplatLds<C>>::type L;
@@ -3214,9 +3269,13 @@ __global__ void __launch_bounds__(kSplatBlock, AMVPT_SPLAT_WAVES) k_splat_multi(
         if constexpr (kRow) {
             wave_put<C, kWin, kF>(P, B.film, L, x, y, vals, valid, coalesce, fb);
         } else {
-            /* deterministic mode runs these instances only (launch_splat) */
-            if (P.film_fx) direct_put<C, kWin, kF>(P, B.film, x, y, vals, valid, coalesce);
-            else block_put<C, kF>(P, B.film, L, buf, x, y, vals, valid, coalesce, fb);
+            if constexpr (kFx) {
+                /* the integer window; direct puts when asked for (block-uniform) */
+                if (P.fx_direct) direct_put<C, kWin, kF>(P, B.film, x, y, vals, valid, coalesce);
+                else block_put<C, kF, true>(P, B.film, L, buf, x, y, vals, valid, coalesce, fb);
+            } else {
+                block_put<C, kF>(P, B.film, L, buf, x, y, vals, valid, coalesce, fb);
+            }
         }
     };
     const uint32_t slot = blockIdx.x * kSplatBlock + threadIdx.x;
@@ -3540,8 +3599,18 @@ void launch_primary(uint32_t cn, size_t lds_tab, size_t lds_bvh, hipStream_t st,
 }
 template <int G>
 void launch_splat(dim3 grid, hipStream_t st, const KParams &P, const DView *V, const Bufs &B, bool diff) {
-    const bool row = P.row_splat && P.C == 4 && !P.film_fx;   /* deterministic: direct puts */
+    const bool row = P.row_splat && P.C == 4 && !P.film_fx;   /* fixed-point film: its block-window instances */
     const bool whole = P.fx0 == 0u && P.fy0 == 0u && P.fw == P.W && P.fh == P.H;
+    if (P.film_fx) {
+#define AMVPT_FX(C_, D_, KF_) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_multi<G, C_, D_, false, true, true, KF_, true>), grid, dim3(kSplatBlock), 0, st, P, V, B)
+        const bool any = P.filt_kind > FILT_GAUSSIAN;
+        if (P.C == 5 && diff) { if (any) AMVPT_FX(5, true, FK_ANY); else AMVPT_FX(5, true, FK_LEGACY); }
+        else if (P.C == 5) { if (any) AMVPT_FX(5, false, FK_ANY); else AMVPT_FX(5, false, FK_LEGACY); }
+        else if (diff) { if (any) AMVPT_FX(4, true, FK_ANY); else AMVPT_FX(4, true, FK_LEGACY); }
+        else { if (any) AMVPT_FX(4, false, FK_ANY); else AMVPT_FX(4, false, FK_LEGACY); }
+#undef AMVPT_FX
+        return;
+    }
     if (P.filt_kind > FILT_GAUSSIAN) {
         /* tent, Mitchell, Catmull-Rom, Lanczos: the row splat of a plain render (render_impl sets row_splat for the
          * filters and parameters that have one), else the block window by the filter's kind */
@@ -3920,13 +3989,15 @@ AMVPT_TU_LOCAL __global__ void __launch_bounds__(256) k_run_counts(const uint8_t
 AMVPT_TU_LOCAL __global__ void k_fixed_resolve(float *film, const unsigned long long *fx, uint64_t n) {
     const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    film[i] += (float) ((double) (long long) fx[i] * (1.0 / kFixScale));
+    film[i] = fixed_resolve_value((int64_t) fx[i], film[i], 1);
 }
 
 amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const amvpt_params *params,
                          const amvpt_lane_set &lanes, const amvpt_film_window &fwin, void *stream,
                          const amvpt_render_opts &opts, amvpt_counters *counters, float *records,
-                         uint32_t record_pass) {
+                         uint32_t record_pass, bool fixed_film) {
+    /* fixed_film (amvpt_render_fixed): fwin.film is the caller's 32.32 integer window and fwin.overflow its integer
+     * list; `film` then only stands for the window's base address (film_fx index = film float index) */
     float *const film = fwin.film;
     if (!scene || !views || !params || !film) { set_error("amvpt_render: null argument"); return AMVPT_ERR_INVALID; }
     RoctxScope range_render("amvpt_render");
@@ -3999,8 +4070,10 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
         return AMVPT_ERR_INVALID;
     }
     const bool whole_film = fwin.x0 == 0 && fwin.y0 == 0 && fwin.width == QW && fwin.height == QH;
-    const bool deterministic = (opts.flags & AMVPT_OPT_DETERMINISTIC) != 0;
-    if (deterministic && !whole_film) {
+    /* the splats add into a fixed-point film: the caller's, or (the flag) a private one resolved into the float film */
+    const bool private_fx = !fixed_film && (opts.flags & AMVPT_OPT_DETERMINISTIC) != 0;
+    const bool deterministic = fixed_film || private_fx;
+    if (private_fx && !whole_film) {
         set_error("amvpt_render: AMVPT_OPT_DETERMINISTIC needs a whole-quilt film window");
         return AMVPT_ERR_UNSUPPORTED;
     }
@@ -4228,7 +4301,7 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
         budget = fr + held > headroom ? fr + held - headroom : 0;
     }
     /* the span-sized buffers below (deterministic film, sampler states, adaptive fill) */
-    const size_t other_need = (deterministic ? (size_t) QW * QH * (Pp.film_alpha ? 5 : 4) * 8 : 0) +
+    const size_t other_need = (private_fx ? (size_t) QW * QH * (Pp.film_alpha ? 5 : 4) * 8 : 0) +
                               (rng_carry ? (size_t) 16 * span : 0) + (do_fill ? (size_t) 6 * span + (1u << 20) : 0);
     const uint64_t min_chunk = std::min<uint64_t>(span, 1ull << 16);
     auto need_of = [&](uint64_t c, int n) { return views_bytes + stats_bytes + set_bytes_of(c) * (size_t) n; };
@@ -4288,12 +4361,17 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
 
     /* deterministic mode: the zeroed 32.32 fixed-point film the splats add into (k_fixed_resolve at the end) */
     const size_t film_floats = (size_t) QW * QH * (Pp.film_alpha ? 5 : 4);
-    if (deterministic) {
+    if (private_fx) {
         { const amvpt_status as_ = arena_reserve(A, A.fx, A.fxbytes, film_floats * 8, "deterministic film"); if (as_ != AMVPT_OK) return as_; }
         HIPCHK(hipMemsetAsync(A.fx, 0, film_floats * 8, st));
         P.film_fx = (unsigned long long *) A.fx;
+    } else if (fixed_film) {
+        P.film_fx = reinterpret_cast<unsigned long long *>(film);   /* accumulated into: no clear, no resolve */
+    }
+    if (deterministic) {
         P.film_base = film;
         P.fx_drops = dstats + 9 * kStatShards;
+        P.fx_direct = (opts.flags & AMVPT_OPT_FIXED_DIRECT) ? 1u : 0u;
     }
 
     /* multi-pass stock path: the per-lane sampler states between passes, two planes used in turn */
@@ -4535,7 +4613,13 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
             const dim3 sgrid((cn + kSplatBlock - 1) / kSplatBlock);
             T.begin(AMVPT_K_SPLAT, st);
             const bool any_filt = P.filt_kind > FILT_GAUSSIAN;   /* FK_ANY instances (tent, Mitchell, Catmull-Rom, Lanczos) */
-            if (G == 1 && P.C == 5 && any_filt) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_single<5, FK_ANY>), sgrid, dim3(kSplatBlock), 0, st, P, B);
+            if (G == 1 && P.film_fx) {
+                if (P.C == 5 && any_filt) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_single<5, FK_ANY, true>), sgrid, dim3(kSplatBlock), 0, st, P, B);
+                else if (any_filt) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_single<4, FK_ANY, true>), sgrid, dim3(kSplatBlock), 0, st, P, B);
+                else if (P.C == 5) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_single<5, FK_LEGACY, true>), sgrid, dim3(kSplatBlock), 0, st, P, B);
+                else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_single<4, FK_LEGACY, true>), sgrid, dim3(kSplatBlock), 0, st, P, B);
+            }
+            else if (G == 1 && P.C == 5 && any_filt) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_single<5, FK_ANY>), sgrid, dim3(kSplatBlock), 0, st, P, B);
             else if (G == 1 && any_filt) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_single<4, FK_ANY>), sgrid, dim3(kSplatBlock), 0, st, P, B);
             else if (G == 1 && P.C == 5) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_single<5>), sgrid, dim3(kSplatBlock), 0, st, P, B);
             else if (G == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_single<4>), sgrid, dim3(kSplatBlock), 0, st, P, B);
@@ -4636,7 +4720,13 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
                 { const amvpt_status rs_ = run_suffix(cs, cn); if (rs_ != AMVPT_OK) return rs_; }
                 const dim3 sgrid((cn + kSplatBlock - 1) / kSplatBlock);
                 T.begin(AMVPT_K_SPLAT, st);
-                if (P.C == 5 && P.filt_kind > FILT_GAUSSIAN) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_adapt<5, FK_ANY>), sgrid, dim3(kSplatBlock), 0, st, P, B);
+                if (P.film_fx) {
+                    if (P.C == 5 && P.filt_kind > FILT_GAUSSIAN) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_adapt<5, FK_ANY, true>), sgrid, dim3(kSplatBlock), 0, st, P, B);
+                    else if (P.filt_kind > FILT_GAUSSIAN) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_adapt<4, FK_ANY, true>), sgrid, dim3(kSplatBlock), 0, st, P, B);
+                    else if (P.C == 5) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_adapt<5, FK_LEGACY, true>), sgrid, dim3(kSplatBlock), 0, st, P, B);
+                    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_adapt<4, FK_LEGACY, true>), sgrid, dim3(kSplatBlock), 0, st, P, B);
+                }
+                else if (P.C == 5 && P.filt_kind > FILT_GAUSSIAN) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_adapt<5, FK_ANY>), sgrid, dim3(kSplatBlock), 0, st, P, B);
                 else if (P.filt_kind > FILT_GAUSSIAN) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_adapt<4, FK_ANY>), sgrid, dim3(kSplatBlock), 0, st, P, B);
                 else if (P.C == 5) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_adapt<5>), sgrid, dim3(kSplatBlock), 0, st, P, B);
                 else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_adapt<4>), sgrid, dim3(kSplatBlock), 0, st, P, B);
@@ -4649,7 +4739,7 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
         }
     }
     arena_release.join();
-    if (deterministic) {
+    if (private_fx) {
         hipLaunchKernelGGL(k_fixed_resolve, dim3((uint32_t) ((film_floats + 255) / 256)), dim3(256), 0, st, film,
                            (const unsigned long long *) A.fx, (uint64_t) film_floats);
         HIPCHK(hipGetLastError());
@@ -4737,6 +4827,55 @@ amvpt_status accumulate_impl(float *quilt, uint32_t qw, uint32_t qh, uint32_t C,
     if (n_ov)
         hipLaunchKernelGGL(k_overflow_apply, dim3((uint32_t) ((n_ov + 255) / 256)), dim3(256), 0, st, quilt,
                            (uint64_t) qw * qh * C, (const uint4 *) ov, n_ov);
+    HIPCHK(hipGetLastError());
+    return AMVPT_OK;
+}
+
+/* amvpt_fixed_accumulate: amvpt_film_accumulate in integers -- plain adds for the window rows (distinct quilt
+ * elements), integer atomics for the overflow entries (indices repeat) */
+AMVPT_TU_LOCAL __global__ void k_fixed_accumulate(int64_t *quilt, uint32_t qw, uint32_t C, const int64_t *win, uint32_t x0,
+                                                  uint32_t y0, uint32_t w) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (i >= w * C) return;
+    int64_t *q = quilt + fixed_window_index(qw, C, x0, y0, y, i);
+    *q = fixed_sum(*q, win[(size_t) y * w * C + i]);
+}
+AMVPT_TU_LOCAL __global__ void k_fixed_overflow_apply(int64_t *quilt, uint64_t n_elems, const uint64_t *e, uint64_t n) {
+    const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t idx = e[2 * i];
+    if (idx < n_elems) atomicAdd(reinterpret_cast<unsigned long long *>(quilt) + idx, (unsigned long long) e[2 * i + 1]);
+}
+amvpt_status fixed_accumulate_impl(int64_t *quilt, uint32_t qw, uint32_t qh, uint32_t C, const int64_t *win, uint32_t x0,
+                                   uint32_t y0, uint32_t w, uint32_t h, const uint64_t *ov, uint64_t n_ov, void *stream) {
+    if (const char *bad = fixed_accumulate_check(quilt, qw, qh, C, win, x0, y0, w, h, ov, n_ov)) {
+        set_error(bad);
+        return AMVPT_ERR_INVALID;
+    }
+    if (h > 65535u || (n_ov + 255) / 256 > 0x7fffffffull) {
+        set_error("amvpt_fixed_accumulate: more than 65535 window rows or 2^39 overflow entries (one launch each)");
+        return AMVPT_ERR_INVALID;
+    }
+    hipStream_t st = (hipStream_t) stream;
+    if (w && h) hipLaunchKernelGGL(k_fixed_accumulate, dim3((w * C + 255) / 256, h), dim3(256), 0, st, quilt, qw, C, win, x0, y0, w);
+    if (n_ov)
+        hipLaunchKernelGGL(k_fixed_overflow_apply, dim3((uint32_t) ((n_ov + 255) / 256)), dim3(256), 0, st, quilt,
+                           (uint64_t) qw * qh * C, ov, n_ov);
+    HIPCHK(hipGetLastError());
+    return AMVPT_OK;
+}
+
+/* amvpt_fixed_resolve: one thread per float, fixed_resolve_value's conversion */
+AMVPT_TU_LOCAL __global__ void k_fixed_resolve_to(const int64_t *fx, float *film, uint64_t n, int add) {
+    const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    film[i] = fixed_resolve_value(fx[i], add ? film[i] : 0.f, add);
+}
+amvpt_status fixed_resolve_impl(const int64_t *fixed, float *film, uint64_t n, int add, void *stream) {
+    if (n && !fixed) { set_error("amvpt_fixed_resolve: fixed is null"); return AMVPT_ERR_INVALID; }
+    if (n && !film) { set_error("amvpt_fixed_resolve: film is null"); return AMVPT_ERR_INVALID; }
+    if ((n + 255) / 256 > 0x7fffffffull) { set_error("amvpt_fixed_resolve: more than 2^39 floats (one launch)"); return AMVPT_ERR_INVALID; }
+    if (n) hipLaunchKernelGGL(k_fixed_resolve_to, dim3((uint32_t) ((n + 255) / 256)), dim3(256), 0, (hipStream_t) stream, fixed, film, n, add);
     HIPCHK(hipGetLastError());
     return AMVPT_OK;
 }

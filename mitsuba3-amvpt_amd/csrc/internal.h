@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/amvpt.h"
+#include "../../include/amvpt_fixed.h"
 #include "dscene.h"
 
 struct amvpt_scene {
@@ -32,7 +33,11 @@ amvpt_status hip_fail(const char *what, int err);
 amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const amvpt_params *params,
                          const amvpt_lane_set &lanes, const amvpt_film_window &film, void *stream,
                          const amvpt_render_opts &opts, amvpt_counters *counters, float *records,
-                         uint32_t record_pass);
+                         uint32_t record_pass, bool fixed_film = false);
+/* amvpt_fixed.h: the fixed-point film's accumulate and resolve (device) */
+amvpt_status fixed_accumulate_impl(int64_t *quilt, uint32_t qw, uint32_t qh, uint32_t C, const int64_t *win, uint32_t x0,
+                                   uint32_t y0, uint32_t w, uint32_t h, const uint64_t *ov, uint64_t n_ov, void *stream);
+amvpt_status fixed_resolve_impl(const int64_t *fixed, float *film, uint64_t n, int add, void *stream);
 amvpt_status develop_impl(const float *film, float *out, uint32_t w, uint32_t h, uint32_t alpha, void *stream);
 amvpt_status release_impl(int device);
 amvpt_status rfilter_eval_impl(const amvpt_params *params, const float *x, uint32_t n, float *out, float *radius);

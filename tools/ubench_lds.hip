@@ -62,6 +62,12 @@ __global__ __launch_bounds__(1024) void k(float* out, int stride) {
             const unsigned lo = (unsigned)__builtin_fmaf(-(float)hi, 4294967296.f, x);
             atomicAdd((unsigned long long*)&s[(a * 2) & (kLds - 2)], ((unsigned long long)hi << 32) + lo);
         }
+        else if (MODE == 17) {   /* win_add_fx (amvpt_render.hip): film_add's f64 conversion and range test, then MODE 14's
+                                  * no-return 64-bit integer add (the fixed-point splat window's cell add) */
+            const double d = (double)(v * (float)(it + 1)) * 4294967296.0;
+            if (__builtin_fabs(d) < 2147483647.0 * 4294967296.0)
+                atomicAdd((unsigned long long*)&s[(a * 2) & (kLds - 2)], (unsigned long long)(long long)__builtin_rint(d));
+        }
         else if (MODE == 8) { float x = s[a]; __builtin_amdgcn_s_waitcnt(0); s[a] = x + v; }
     }
     __syncthreads();
@@ -93,6 +99,7 @@ int main() {
         run<11>("ds_add_f64 distinct", 1, bs);
         run<15>("ds_add_f64 distinct 8B-stride", 1, bs);
         run<16>("fixed-point cvt + u64 8B-stride", 1, bs);
+        run<17>("film_add f64 cvt + ds_add_u64 8B", 1, bs);
         run<12>("fixed-point cvt + ds_add_u64", 1, bs);
         run<13>("CAS64 pair add distinct", 1, bs);
         run<4>("ds_add_u32 distinct", 1, bs);
