@@ -19,6 +19,12 @@
  *
  * All queues and records are SoA float4 streams in HBM (16 B per lane per
  * stream: one dwordx4 load/store per lane, 1 KiB per wave instruction).
+ *
+ * Layout: tuning constants, the kernels, then per kernel family one table of its instances (kExtend, kShadow,
+ * kBounce, kSuffixFused, kBinSort, kSplatLane; per group size those inside launch_primary<G> / launch_splat<G>)
+ * with one lookup (find_inst) for every launch site, then the host orchestration: render_impl is the pipeline,
+ * its steps (make_plan, size_arena, reserve_span_buffers, carve_sets, run_chunk, run_suffix, run_fill,
+ * read_counters) are functions of their own.
  */
 #include <hip/hip_runtime.h>
 #include <rocprofiler-sdk-roctx/roctx.h>
@@ -36,11 +42,11 @@
 #include "dbsdf.h"
 #include "dfixed.h"
 
-/* non-template kernels get internal linkage in the k_shadow translation unit (amvpt_shadow.hip) */
-#if defined(AMVPT_SHADOW_TU) || defined(AMVPT_GROUP_TU)
-#define AMVPT_TU_LOCAL static
-#else
-#define AMVPT_TU_LOCAL
+/* The main unit: this file compiled as itself.  amvpt_shadow.hip (AMVPT_SHADOW_TU) and amvpt_group_*.hip
+ * (AMVPT_GROUP_TU) include it for the templates and compile only their own instances; the non-template kernels, the
+ * other instance tables and the host orchestration belong to the main unit alone. */
+#if !defined(AMVPT_SHADOW_TU) && !defined(AMVPT_GROUP_TU)
+#define AMVPT_MAIN_TU 1
 #endif
 
 /*
@@ -151,7 +157,7 @@
 
 namespace amvpt {
 
-#if !defined(AMVPT_SHADOW_TU) && !defined(AMVPT_GROUP_TU)
+#ifdef AMVPT_MAIN_TU
 /* 0 = automatic: 2^26 lanes, halved while the chunk's arena would exceed 48 GB (of the 288 GB of HBM; config M:
  * 26 GB at 2^26, 1598/1605 -> 1614/1621 Msamples/s against 2^25 chunks, r03zg: fewer fused-suffix tails).
  * Earlier sweep at 24 GB:
@@ -1669,7 +1675,8 @@ AD void lane_pixel(const KParams &P, uint32_t lane, int &px, int &py) {
     px = (int) (pix - P.W * y + P.off_x);
 }
 
-AMVPT_TU_LOCAL __global__ void __launch_bounds__(256) k_raygen_single(KParams P, const DView *V, Bufs B) {
+#ifdef AMVPT_MAIN_TU
+__global__ void __launch_bounds__(256) k_raygen_single(KParams P, const DView *V, Bufs B) {
     const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
     bool ok = slot < P.chunk_n;
     PathState s;
@@ -1701,6 +1708,7 @@ AMVPT_TU_LOCAL __global__ void __launch_bounds__(256) k_raygen_single(KParams P,
     if (ok) store_state(B.q_out, qslot, s);
     if (B.stats) stat_add(B.stats, 8, ok ? 1ull : 0ull);
 }
+#endif
 
 /* ------------------------------------------------------------------ */
 /* Adaptive fill (mvpath_multi.h:79-115): lanes whose primary vertex had at most one
@@ -1722,7 +1730,8 @@ AD void lane_sample_pos(const KParams &P, uint32_t lane, float &sx, float &sy, f
     if (P.needs_ap) { apx = rng.next_1d(); apy = rng.next_1d(); }   /* nested_gather(aperture_sample) */
 }
 
-AMVPT_TU_LOCAL __global__ void __launch_bounds__(256) k_raygen_adapt(KParams P, const DView *V, Bufs B) {
+#ifdef AMVPT_MAIN_TU
+__global__ void __launch_bounds__(256) k_raygen_adapt(KParams P, const DView *V, Bufs B) {
     const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
     bool ok = slot < P.chunk_n;
     PathState s;
@@ -1752,6 +1761,7 @@ AMVPT_TU_LOCAL __global__ void __launch_bounds__(256) k_raygen_adapt(KParams P, 
     if (ok) store_state(B.q_out, qslot, s);
     if (B.stats) stat_add(B.stats, 8, ok ? 1ull : 0ull);
 }
+#endif
 
 /* ------------------------------------------------------------------ */
 /* k_bounce: one loop iteration (mvpath_multi.h:563-686 == mvpath_single.h:130-275) */
@@ -3426,8 +3436,9 @@ __global__ void __launch_bounds__(kSplatBlock, AMVPT_SPLAT_WAVES) k_splat_multi(
     }
 }
 
+#ifdef AMVPT_MAIN_TU
 /* develop: rgb / W (hdrfilm.cpp:400) */
-AMVPT_TU_LOCAL __global__ void k_develop(const float *film, float *out, uint32_t npx, uint32_t alpha) {
+__global__ void k_develop(const float *film, float *out, uint32_t npx, uint32_t alpha) {
     uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= npx) return;
     uint32_t C = alpha ? 5u : 4u, T = alpha ? 4u : 3u;
@@ -3436,6 +3447,7 @@ AMVPT_TU_LOCAL __global__ void k_develop(const float *film, float *out, uint32_t
     float d = w == 0.f ? 1.f : w;
     for (uint32_t c = 0; c < T; ++c) out[(size_t) p * T + c] = src[c] / d;
 }
+#endif
 
 /*
  * k_shadow launcher.  It is defined in its own translation unit (amvpt_shadow.hip
@@ -3443,18 +3455,58 @@ AMVPT_TU_LOCAL __global__ void k_develop(const float *film, float *out, uint32_t
  * k_shadow is the one kernel that is faster with it (71 vs 80 ms per config-M frame),
  * while the rest of this file is built with -fno-slp-vectorize (see Makefile).
  */
-void launch_shadow(int walk, bool bin, dim3 grid, size_t lds, hipStream_t st, const KParams &P, const DScene *dS, const Bufs &B)
+/* ------------------------------------------------------------------ */
+/* Kernel instances                                                   */
+/* ------------------------------------------------------------------ */
+
+/*
+ * The instances the library contains are the lines of the tables below and of launch_primary<G> / launch_splat<G>:
+ * one table per kernel family, one line per instance, its selector values being its template arguments.  A launch
+ * site normalises its selectors (which values make no difference to the family) and looks the instance up; a
+ * selector no line lists fails the render with AMVPT_ERR_UNSUPPORTED.  The tables are explicit because the families
+ * need far fewer instances than the cross products of their arguments, and every instance costs build time.
+ */
+typedef void (*scene_kernel)(KParams, const DScene *, Bufs);                      /* k_extend, k_shadow, k_bounce, k_suffix_fused */
+typedef void (*lane_kernel)(KParams, Bufs);                                       /* k_bin_sort, k_splat_single, k_splat_adapt */
+typedef void (*primary_kernel)(KParams, const DScene *, const DView *, Bufs);     /* the primary vertex's kernels */
+typedef void (*view_kernel)(KParams, const DView *, Bufs);                        /* k_splat_multi */
+constexpr int kMaxSel = 7;
+template <class Fn> struct Inst {
+    int sel[kMaxSel];
+    Fn fn;   /* null: no such instance at this group size */
+};
+#define AMVPT_INST(K_, ...) {{__VA_ARGS__}, K_<__VA_ARGS__>}
+#define AMVPT_INST_G(K_, ...) {{__VA_ARGS__}, K_<G, __VA_ARGS__>}
+template <class Fn, size_t N>
+amvpt_status find_inst(const char *family, const Inst<Fn> (&tab)[N], std::initializer_list<int> sel, Fn &fn) {
+    for (const Inst<Fn> &e : tab)
+        if (e.fn && std::equal(sel.begin(), sel.end(), e.sel)) { fn = e.fn; return AMVPT_OK; }
+    std::string s;
+    for (int v : sel) s += (s.empty() ? "" : ", ") + std::to_string(v);
+    set_error(std::string("amvpt_render: no ") + family + " instance for selector (" + s + ")");
+    return AMVPT_ERR_UNSUPPORTED;
+}
+inline bool is_lane_walk(int walk) { return walk == WALK_LANE || walk == WALK_LANE_NS || walk == WALK_LANE_TRI; }
+
+/*
+ * k_shadow by (walk, binned rays; bin applies to the per-lane walks only).  Its instances are compiled in a unit of
+ * their own (amvpt_shadow.hip includes this file with AMVPT_SHADOW_TU), WITH the SLP vectorizer: k_shadow is the one
+ * kernel that is faster with it (71 vs 80 ms per config-M frame), while the rest of this file is built with
+ * -fno-slp-vectorize (see Makefile).
+ */
+amvpt_status launch_shadow(int walk, bool bin, dim3 grid, size_t lds, hipStream_t st, const KParams &P, const DScene *dS,
+                           const Bufs &B)
 #ifdef AMVPT_SHADOW_TU
 {
-    if (bin && walk == WALK_LANE_TRI) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_shadow<WALK_LANE_TRI, true>), grid, dim3(256), lds, st, P, dS, B);
-    else if (bin && walk == WALK_LANE_NS) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_shadow<WALK_LANE_NS, true>), grid, dim3(256), lds, st, P, dS, B);
-    else if (bin && walk == WALK_LANE) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_shadow<WALK_LANE, true>), grid, dim3(256), lds, st, P, dS, B);
-    else if (walk == WALK_BRUTE_NS) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_shadow<WALK_BRUTE_NS>), grid, dim3(256), lds, st, P, dS, B);
-    else if (walk == WALK_BRUTE) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_shadow<WALK_BRUTE>), grid, dim3(256), lds, st, P, dS, B);
-    else if (walk == WALK_UNI) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_shadow<WALK_UNI>), grid, dim3(256), lds, st, P, dS, B);
-    else if (walk == WALK_LANE_TRI) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_shadow<WALK_LANE_TRI>), grid, dim3(256), lds, st, P, dS, B);
-    else if (walk == WALK_LANE_NS) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_shadow<WALK_LANE_NS>), grid, dim3(256), lds, st, P, dS, B);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_shadow<WALK_LANE>), grid, dim3(256), lds, st, P, dS, B);
+    static const Inst<scene_kernel> kShadow[] = {
+        AMVPT_INST(k_shadow, WALK_LANE_TRI, true), AMVPT_INST(k_shadow, WALK_LANE_NS, true), AMVPT_INST(k_shadow, WALK_LANE, true),
+        AMVPT_INST(k_shadow, WALK_BRUTE_NS, false), AMVPT_INST(k_shadow, WALK_BRUTE, false), AMVPT_INST(k_shadow, WALK_UNI, false),
+        AMVPT_INST(k_shadow, WALK_LANE_TRI, false), AMVPT_INST(k_shadow, WALK_LANE_NS, false), AMVPT_INST(k_shadow, WALK_LANE, false)};
+    scene_kernel fn = nullptr;
+    const amvpt_status s = find_inst("k_shadow", kShadow, {walk, bin && is_lane_walk(walk)}, fn);
+    if (s != AMVPT_OK) return s;
+    hipLaunchKernelGGL(fn, grid, dim3(256), lds, st, P, dS, B);
+    return AMVPT_OK;
 }
 #else
 ;
@@ -3517,14 +3569,16 @@ struct KTimer {
 };
 
 /*
- * Group-size instances.  The G-dependent launchers (and the ~20 kernels each pulls in) are
- * explicitly instantiated in the translation units csrc/amvpt_group_*.hip (this file included
- * with AMVPT_GROUP_TU and AMVPT_GROUP_LIST), so the instances compile in parallel; this unit
- * only declares them.  k_prim_hit does not depend on G: its launcher lives here.
+ * Group-size instances.  The G-dependent launchers are explicitly instantiated in the translation
+ * units csrc/amvpt_group_*.hip (this file included with AMVPT_GROUP_TU and AMVPT_GROUP_LIST), so
+ * the instances compile in parallel; the main unit only declares them.  Each launcher holds the
+ * tables of its kernel families for its G (k_prim_hit_req, k_prim_req, k_vis and k_mv_primary in
+ * launch_primary<G>, k_splat_multi in launch_splat<G>): 51 kernels per G >= 2, 50 for the runtime
+ * sizes.  k_prim_hit does not depend on G: its launcher lives in the main unit.
  */
 void launch_prim_hit(bool uni, dim3 grid, size_t lds_bvh, hipStream_t st, const KParams &P, const DScene *S,
                      const DView *V, const Bufs &B)
-#if !defined(AMVPT_SHADOW_TU) && !defined(AMVPT_GROUP_TU)
+#ifdef AMVPT_MAIN_TU
 {
     if (uni) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_prim_hit<true>), grid, dim3(256), lds_bvh, st, P, S, V, B);
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_prim_hit<false>), grid, dim3(256), lds_bvh, st, P, S, V, B);
@@ -3534,126 +3588,140 @@ void launch_prim_hit(bool uni, dim3 grid, size_t lds_bvh, hipStream_t st, const 
 #endif
 #ifdef AMVPT_GROUP_TU
 template <int G> inline int group_size_host(const KParams &P) { return G > 0 ? G : (int) P.G; }
+/* the fused primary vertex exists for the compile-time group sizes only */
+template <int G> constexpr primary_kernel fused_primary() {
+    if constexpr (G >= 2) return k_mv_primary<G, true, true, false, true>;
+    else return nullptr;
+}
 /* the primary wavefronts of one chunk: k_prim_hit -> k_prim_req -> k_vis -> k_mv_primary */
 template <int G>
-void launch_primary(uint32_t cn, size_t lds_tab, size_t lds_bvh, hipStream_t st, const KParams &P,
-                           const DScene *S, const DView *V, const Bufs &B, bool tab, bool uni, bool diff, KTimer &T) {
+amvpt_status launch_primary(uint32_t cn, size_t lds_tab, size_t lds_bvh, hipStream_t st, const KParams &P,
+                            const DScene *S, const DView *V, const Bufs &B, bool tab, bool uni, bool diff, KTimer &T) {
+    /* (tables in LDS, all-diffuse, spheres: 0 none, 1 tested in place, 2 deferred; 1 whenever the tables are not
+     * staged).  Sphere-free scenes: the instances without float64 sphere code (the Cornell and mesh benches);
+     * scenes of <= 64 spheres: the deferred sphere tests (P.sph, dgeom.h) */
+    static const Inst<primary_kernel> kPrimHitReq[] = {
+        AMVPT_INST_G(k_prim_hit_req, true, true, 0), AMVPT_INST_G(k_prim_hit_req, true, false, 0),
+        AMVPT_INST_G(k_prim_hit_req, true, true, 2), AMVPT_INST_G(k_prim_hit_req, true, false, 2),
+        AMVPT_INST_G(k_prim_hit_req, true, true, 1), AMVPT_INST_G(k_prim_hit_req, true, false, 1),
+        AMVPT_INST_G(k_prim_hit_req, false, true, 1), AMVPT_INST_G(k_prim_hit_req, false, false, 1)};
+    /* (tables in LDS, all-diffuse) */
+    static const Inst<primary_kernel> kPrimReq[] = {
+        AMVPT_INST_G(k_prim_req, true, true), AMVPT_INST_G(k_prim_req, true, false),
+        AMVPT_INST_G(k_prim_req, false, true), AMVPT_INST_G(k_prim_req, false, false)};
+    /* (wave-uniform walk, spheres; 1 on the per-lane walk) */
+    static const Inst<primary_kernel> kVis[] = {
+        AMVPT_INST_G(k_vis, true, 0), AMVPT_INST_G(k_vis, true, 2), AMVPT_INST_G(k_vis, true, 1), AMVPT_INST_G(k_vis, false, 1)};
+    /* (tables in LDS, all-diffuse, the all-diffuse waves of a mixed scene, fused vertex) */
+    static const Inst<primary_kernel> kMvPrimary[] = {
+        {{true, true, false, true}, fused_primary<G>()},
+        AMVPT_INST_G(k_mv_primary, true, true, false, false), AMVPT_INST_G(k_mv_primary, false, true, false, false),
+        AMVPT_INST_G(k_mv_primary, true, false, true, false), AMVPT_INST_G(k_mv_primary, false, false, true, false),
+        AMVPT_INST_G(k_mv_primary, true, false, false, false), AMVPT_INST_G(k_mv_primary, false, false, false, false)};
     constexpr int kPB = prim_block<G>(), kVW = vis_waves<G>();
     const dim3 g256((cn + 255) / 256), g64((cn + 63) / 64), gp((cn + kPB - 1) / kPB);
     const size_t lds_view = B.vstate ? 0u : (size_t) (diff ? vs_fields<G, true>() : vs_fields<G, false>()) * group_size_host<G>(P) * kPB * sizeof(float);
+    primary_kernel fn = nullptr, fn_dw = nullptr;
+    amvpt_status s = AMVPT_OK;
     if constexpr (G >= 2) {
         /* sphere-free all-diffuse scenes walked wave-uniformly, compile-time groups: the whole vertex in one launch
          * (k_mv_primary's kFuse instance) -- the request code evaluated the functions k_mv_primary evaluates again,
          * only to hand k_vis its rays.  AMVPT_OPT_SPLIT_PRIMARY keeps the three launches. */
         if (uni && !P.split_prim && tab && diff && P.sph == 0) {
+            if ((s = find_inst("k_mv_primary", kMvPrimary, {tab, diff, false, true}, fn)) != AMVPT_OK) return s;
             T.begin(AMVPT_K_MV_PRIMARY, st);
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mv_primary<G, true, true, false, true>), gp, dim3(kPB), lds_tab + lds_view, st, P, S, V, B);
+            hipLaunchKernelGGL(fn, gp, dim3(kPB), lds_tab + lds_view, st, P, S, V, B);
             T.end(st);
-            return;
+            return AMVPT_OK;
         }
     }
     if (uni) {
+        if ((s = find_inst("k_prim_hit_req", kPrimHitReq, {tab, diff, tab ? (int) P.sph : 1}, fn)) != AMVPT_OK) return s;
         T.begin(AMVPT_K_PRIM_HIT, st);
-        /* sphere-free scenes: the instances without float64 sphere code (the Cornell and mesh benches); scenes of
-         * <= 64 spheres: the deferred sphere tests (P.sph, dgeom.h) */
-        if (tab && diff && P.sph == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_prim_hit_req<G, true, true, 0>), g256, dim3(256), lds_tab, st, P, S, V, B);
-        else if (tab && P.sph == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_prim_hit_req<G, true, false, 0>), g256, dim3(256), lds_tab, st, P, S, V, B);
-        else if (tab && diff && P.sph == 2) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_prim_hit_req<G, true, true, 2>), g256, dim3(256), lds_tab, st, P, S, V, B);
-        else if (tab && P.sph == 2) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_prim_hit_req<G, true, false, 2>), g256, dim3(256), lds_tab, st, P, S, V, B);
-        else if (tab && diff) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_prim_hit_req<G, true, true>), g256, dim3(256), lds_tab, st, P, S, V, B);
-        else if (tab) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_prim_hit_req<G, true, false>), g256, dim3(256), lds_tab, st, P, S, V, B);
-        else if (diff) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_prim_hit_req<G, false, true>), g256, dim3(256), lds_tab, st, P, S, V, B);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_prim_hit_req<G, false, false>), g256, dim3(256), lds_tab, st, P, S, V, B);
+        hipLaunchKernelGGL(fn, g256, dim3(256), lds_tab, st, P, S, V, B);
         T.end(st);
     } else {
+        if ((s = find_inst("k_prim_req", kPrimReq, {tab, diff}, fn)) != AMVPT_OK) return s;
         T.begin(AMVPT_K_PRIM_HIT, st);
         launch_prim_hit(uni, g256, lds_bvh, st, P, S, V, B);
         T.end(st);
         T.begin(AMVPT_K_PRIM_REQ, st);
-        if (tab && diff) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_prim_req<G, true, true>), g256, dim3(256), lds_tab, st, P, S, V, B);
-        else if (tab) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_prim_req<G, true, false>), g256, dim3(256), lds_tab, st, P, S, V, B);
-        else if (diff) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_prim_req<G, false, true>), g256, dim3(256), lds_tab, st, P, S, V, B);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_prim_req<G, false, false>), g256, dim3(256), lds_tab, st, P, S, V, B);
+        hipLaunchKernelGGL(fn, g256, dim3(256), lds_tab, st, P, S, V, B);
         T.end(st);
     }
+    if ((s = find_inst("k_vis", kVis, {uni, uni ? (int) P.sph : 1}, fn)) != AMVPT_OK) return s;
     T.begin(AMVPT_K_VIS, st);
     constexpr bool kVisPairs = vis_pairs<G, true>();
-    const dim3 gvis = kVisPairs ? dim3((cn + 64 * AMVPT_VIS_RAYS - 1) / (64 * AMVPT_VIS_RAYS)) : g64;
-    if (uni && P.sph == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_vis<G, true, 0>), gvis, dim3(64 * kVW), lds_bvh, st, P, S, V, B);
-    else if (uni && P.sph == 2) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_vis<G, true, 2>), gvis, dim3(64 * kVW), lds_bvh, st, P, S, V, B);
-    else if (uni) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_vis<G, true>), gvis, dim3(64 * kVW), lds_bvh, st, P, S, V, B);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_vis<G, false>), g64, dim3(64 * kVW), lds_bvh, st, P, S, V, B);
+    const dim3 gvis = uni && kVisPairs ? dim3((cn + 64 * AMVPT_VIS_RAYS - 1) / (64 * AMVPT_VIS_RAYS)) : g64;
+    hipLaunchKernelGGL(fn, gvis, dim3(64 * kVW), lds_bvh, st, P, S, V, B);
     T.end(st);
+    /* mixed-material scenes: the all-diffuse waves first, with the all-diffuse body's smaller per-view LDS state */
+    if (!diff && (s = find_inst("k_mv_primary", kMvPrimary, {tab, false, true, false}, fn_dw)) != AMVPT_OK) return s;
+    if ((s = find_inst("k_mv_primary", kMvPrimary, {tab, diff, false, false}, fn)) != AMVPT_OK) return s;
     T.begin(AMVPT_K_MV_PRIMARY, st);
-    if (tab && diff) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mv_primary<G, true, true>), gp, dim3(kPB), lds_tab + lds_view, st, P, S, V, B);
-    else if (diff) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mv_primary<G, false, true>), gp, dim3(kPB), lds_tab + lds_view, st, P, S, V, B);
-    else {
-        /* the all-diffuse waves first, with the all-diffuse body's smaller per-view LDS state */
+    if (fn_dw) {
         const size_t lds_dw = B.vstate ? 0u : (size_t) vs_fields<G, true>() * group_size_host<G>(P) * kPB * sizeof(float);
-        if (tab) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mv_primary<G, true, false, true>), gp, dim3(kPB), lds_tab + lds_dw, st, P, S, V, B);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mv_primary<G, false, false, true>), gp, dim3(kPB), lds_tab + lds_dw, st, P, S, V, B);
-        if (tab) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mv_primary<G, true, false>), gp, dim3(kPB), lds_tab + lds_view, st, P, S, V, B);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mv_primary<G, false, false>), gp, dim3(kPB), lds_tab + lds_view, st, P, S, V, B);
+        hipLaunchKernelGGL(fn_dw, gp, dim3(kPB), lds_tab + lds_dw, st, P, S, V, B);
     }
+    hipLaunchKernelGGL(fn, gp, dim3(kPB), lds_tab + lds_view, st, P, S, V, B);
     T.end(st);
+    return AMVPT_OK;
 }
+/* k_splat_multi by (C, all-diffuse records, row splat, film window, records / debug, filter form, fixed-point film) */
 template <int G>
-void launch_splat(dim3 grid, hipStream_t st, const KParams &P, const DView *V, const Bufs &B, bool diff) {
-    const bool row = P.row_splat && P.C == 4 && !P.film_fx;   /* fixed-point film: its block-window instances */
+amvpt_status launch_splat(dim3 grid, hipStream_t st, const KParams &P, const DView *V, const Bufs &B, bool diff) {
+    static const Inst<view_kernel> kSplatMulti[] = {
+        /* the fixed-point film: the block window */
+        AMVPT_INST_G(k_splat_multi, 5, true, false, true, true, FK_ANY, true), AMVPT_INST_G(k_splat_multi, 5, true, false, true, true, FK_LEGACY, true),
+        AMVPT_INST_G(k_splat_multi, 5, false, false, true, true, FK_ANY, true), AMVPT_INST_G(k_splat_multi, 5, false, false, true, true, FK_LEGACY, true),
+        AMVPT_INST_G(k_splat_multi, 4, true, false, true, true, FK_ANY, true), AMVPT_INST_G(k_splat_multi, 4, true, false, true, true, FK_LEGACY, true),
+        AMVPT_INST_G(k_splat_multi, 4, false, false, true, true, FK_ANY, true), AMVPT_INST_G(k_splat_multi, 4, false, false, true, true, FK_LEGACY, true),
+        /* tent, Mitchell, Catmull-Rom: the row splat of a plain render */
+        AMVPT_INST_G(k_splat_multi, 4, true, true, false, false, FK_TENT, false), AMVPT_INST_G(k_splat_multi, 4, false, true, false, false, FK_TENT, false),
+        AMVPT_INST_G(k_splat_multi, 4, true, true, false, false, FK_MITCHELL, false), AMVPT_INST_G(k_splat_multi, 4, false, true, false, false, FK_MITCHELL, false),
+        AMVPT_INST_G(k_splat_multi, 4, true, true, false, false, FK_CATMULLROM, false), AMVPT_INST_G(k_splat_multi, 4, false, true, false, false, FK_CATMULLROM, false),
+        /* those and Lanczos otherwise: the block window by the filter's kind */
+        AMVPT_INST_G(k_splat_multi, 5, true, false, true, true, FK_ANY, false), AMVPT_INST_G(k_splat_multi, 5, false, false, true, true, FK_ANY, false),
+        AMVPT_INST_G(k_splat_multi, 4, true, false, true, true, FK_ANY, false), AMVPT_INST_G(k_splat_multi, 4, false, false, true, true, FK_ANY, false),
+        /* box and Gaussian: the block window; RGBW films with >= 16 samples per pixel the row splat, without the
+         * window test on a whole-quilt film, without the record and debug paths in a plain render */
+        AMVPT_INST_G(k_splat_multi, 5, true, false, true, true, FK_LEGACY, false), AMVPT_INST_G(k_splat_multi, 5, false, false, true, true, FK_LEGACY, false),
+        AMVPT_INST_G(k_splat_multi, 4, true, true, false, false, FK_LEGACY, false), AMVPT_INST_G(k_splat_multi, 4, false, true, false, false, FK_LEGACY, false),
+        AMVPT_INST_G(k_splat_multi, 4, true, true, false, true, FK_LEGACY, false), AMVPT_INST_G(k_splat_multi, 4, false, true, false, true, FK_LEGACY, false),
+        AMVPT_INST_G(k_splat_multi, 4, true, true, true, true, FK_LEGACY, false), AMVPT_INST_G(k_splat_multi, 4, false, true, true, true, FK_LEGACY, false),
+        AMVPT_INST_G(k_splat_multi, 4, true, false, true, true, FK_LEGACY, false), AMVPT_INST_G(k_splat_multi, 4, false, false, true, true, FK_LEGACY, false)};
+    const bool fx = P.film_fx != nullptr, any = P.filt_kind > FILT_GAUSSIAN;
+    const bool row = P.row_splat && P.C == 4 && !fx;   /* fixed-point film: its block-window instances */
     const bool whole = P.fx0 == 0u && P.fy0 == 0u && P.fw == P.W && P.fh == P.H;
-    if (P.film_fx) {
-#define AMVPT_FX(C_, D_, KF_) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_multi<G, C_, D_, false, true, true, KF_, true>), grid, dim3(kSplatBlock), 0, st, P, V, B)
-        const bool any = P.filt_kind > FILT_GAUSSIAN;
-        if (P.C == 5 && diff) { if (any) AMVPT_FX(5, true, FK_ANY); else AMVPT_FX(5, true, FK_LEGACY); }
-        else if (P.C == 5) { if (any) AMVPT_FX(5, false, FK_ANY); else AMVPT_FX(5, false, FK_LEGACY); }
-        else if (diff) { if (any) AMVPT_FX(4, true, FK_ANY); else AMVPT_FX(4, true, FK_LEGACY); }
-        else { if (any) AMVPT_FX(4, false, FK_ANY); else AMVPT_FX(4, false, FK_LEGACY); }
-#undef AMVPT_FX
-        return;
-    }
-    if (P.filt_kind > FILT_GAUSSIAN) {
-        /* tent, Mitchell, Catmull-Rom, Lanczos: the row splat of a plain render (render_impl sets row_splat for the
-         * filters and parameters that have one), else the block window by the filter's kind */
-        const bool plain_row = row && whole && !P.record && !P.debug;
-#define AMVPT_ROW_F(KF_)                                                                                                 \
-        if (diff) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_multi<G, 4, true, true, false, false, KF_>), grid, dim3(kSplatBlock), 0, st, P, V, B); \
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_multi<G, 4, false, true, false, false, KF_>), grid, dim3(kSplatBlock), 0, st, P, V, B);
-        if (plain_row && P.filt_kind == FILT_TENT) { AMVPT_ROW_F(FK_TENT) }
-        else if (plain_row && P.filt_kind == FILT_MITCHELL) { AMVPT_ROW_F(FK_MITCHELL) }
-        else if (plain_row && P.filt_kind == FILT_CATMULLROM) { AMVPT_ROW_F(FK_CATMULLROM) }
-#undef AMVPT_ROW_F
-        else if (P.C == 5 && diff) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_multi<G, 5, true, false, true, true, FK_ANY>), grid, dim3(kSplatBlock), 0, st, P, V, B);
-        else if (P.C == 5) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_multi<G, 5, false, false, true, true, FK_ANY>), grid, dim3(kSplatBlock), 0, st, P, V, B);
-        else if (diff) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_multi<G, 4, true, false, true, true, FK_ANY>), grid, dim3(kSplatBlock), 0, st, P, V, B);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_multi<G, 4, false, false, true, true, FK_ANY>), grid, dim3(kSplatBlock), 0, st, P, V, B);
-        return;
-    }
-    if (P.C == 5 && diff) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_multi<G, 5, true, false>), grid, dim3(kSplatBlock), 0, st, P, V, B);
-    else if (P.C == 5) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_multi<G, 5, false, false>), grid, dim3(kSplatBlock), 0, st, P, V, B);
-    else if (diff && row && whole && !P.record && !P.debug) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_multi<G, 4, true, true, false, false>), grid, dim3(kSplatBlock), 0, st, P, V, B);
-    else if (row && whole && !P.record && !P.debug) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_multi<G, 4, false, true, false, false>), grid, dim3(kSplatBlock), 0, st, P, V, B);
-    else if (diff && row && whole) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_multi<G, 4, true, true, false>), grid, dim3(kSplatBlock), 0, st, P, V, B);
-    else if (row && whole) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_multi<G, 4, false, true, false>), grid, dim3(kSplatBlock), 0, st, P, V, B);
-    else if (diff && row) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_multi<G, 4, true, true>), grid, dim3(kSplatBlock), 0, st, P, V, B);
-    else if (row) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_multi<G, 4, false, true>), grid, dim3(kSplatBlock), 0, st, P, V, B);
-    else if (diff) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_multi<G, 4, true, false>), grid, dim3(kSplatBlock), 0, st, P, V, B);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_multi<G, 4, false, false>), grid, dim3(kSplatBlock), 0, st, P, V, B);
+    const bool plain = row && whole && !P.record && !P.debug;
+    /* tent, Mitchell, Catmull-Rom: the row splat of a plain render (make_plan sets row_splat for the filters and
+     * parameters that have one) */
+    const int row_kf = !any ? FK_LEGACY : !plain ? FK_ANY : P.filt_kind == FILT_TENT ? FK_TENT
+                       : P.filt_kind == FILT_MITCHELL ? FK_MITCHELL : P.filt_kind == FILT_CATMULLROM ? FK_CATMULLROM : FK_ANY;
+    const bool k_row = row && row_kf != FK_ANY;
+    const int kf = k_row ? row_kf : any ? FK_ANY : FK_LEGACY;
+    view_kernel fn = nullptr;
+    const amvpt_status s = find_inst("k_splat_multi", kSplatMulti,
+                                     {P.C == 5 ? 5 : 4, diff, k_row, !(k_row && whole), !(k_row && plain), kf, fx}, fn);
+    if (s != AMVPT_OK) return s;
+    hipLaunchKernelGGL(fn, grid, dim3(kSplatBlock), 0, st, P, V, B);
+    return AMVPT_OK;
 }
 #define AMVPT_GROUP_INST(G_)                                                                                      \
-    template void launch_primary<G_>(uint32_t, size_t, size_t, hipStream_t, const KParams &, const DScene *,            \
-                                     const DView *, const Bufs &, bool, bool, bool, KTimer &);                          \
-    template void launch_splat<G_>(dim3, hipStream_t, const KParams &, const DView *, const Bufs &, bool);
+    template amvpt_status launch_primary<G_>(uint32_t, size_t, size_t, hipStream_t, const KParams &, const DScene *,   \
+                                             const DView *, const Bufs &, bool, bool, bool, KTimer &);                 \
+    template amvpt_status launch_splat<G_>(dim3, hipStream_t, const KParams &, const DView *, const Bufs &, bool);
 AMVPT_GROUP_LIST(AMVPT_GROUP_INST)
 #undef AMVPT_GROUP_INST
 #else
 template <int G>
-void launch_primary(uint32_t cn, size_t lds_tab, size_t lds_bvh, hipStream_t st, const KParams &P, const DScene *S,
-                    const DView *V, const Bufs &B, bool tab, bool uni, bool diff, KTimer &T);
+amvpt_status launch_primary(uint32_t cn, size_t lds_tab, size_t lds_bvh, hipStream_t st, const KParams &P, const DScene *S,
+                            const DView *V, const Bufs &B, bool tab, bool uni, bool diff, KTimer &T);
 template <int G>
-void launch_splat(dim3 grid, hipStream_t st, const KParams &P, const DView *V, const Bufs &B, bool diff);
+amvpt_status launch_splat(dim3 grid, hipStream_t st, const KParams &P, const DView *V, const Bufs &B, bool diff);
 #endif
 
-#if !defined(AMVPT_SHADOW_TU) && !defined(AMVPT_GROUP_TU) && !defined(AMVPT_KERNEL_PROBE)
+#if defined(AMVPT_MAIN_TU) && !defined(AMVPT_KERNEL_PROBE)
 /* ------------------------------------------------------------------ */
 /* Host orchestration                                                 */
 /* ------------------------------------------------------------------ */
@@ -3661,16 +3729,11 @@ void launch_splat(dim3 grid, hipStream_t st, const KParams &P, const DView *V, c
 static void plan(const amvpt_params &P, uint32_t &spp, uint32_t &spp_pp, uint32_t &n_passes, uint64_t &L) {
     uint32_t s = P.spp ? P.spp : 1;
     uint64_t px = (uint64_t) P.film_width * P.film_height;
-    if (P.integrator == AMVPT_INTEGRATOR_MVPATH) {
-        spp_pp = P.spp_pass_lim ? std::min(P.spp_pass_lim, s) : s;
-        n_passes = s / spp_pp;
-        s = n_passes * spp_pp;
-    } else {
-        /* SamplingIntegrator::render (integrator.cpp:137-146): samples_per_pass travels in spp_pass_lim
-         * (0 = unset); render_impl refuses an spp it does not divide, as the reference throws */
-        spp_pp = P.spp_pass_lim ? std::min(P.spp_pass_lim, s) : s;
-        n_passes = s / spp_pp;
-    }
+    spp_pp = P.spp_pass_lim ? std::min(P.spp_pass_lim, s) : s;
+    n_passes = s / spp_pp;
+    /* mvpath renders whole passes.  SamplingIntegrator::render (integrator.cpp:137-146): samples_per_pass travels
+     * in spp_pass_lim (0 = unset); plan_lanes refuses an spp it does not divide, as the reference throws */
+    if (P.integrator == AMVPT_INTEGRATOR_MVPATH) s = n_passes * spp_pp;
     uint64_t wf = px * spp_pp;
     if (wf > 0xffffffffull) {
         spp_pp /= (uint32_t) ((wf + 0xffffffffull - 1) / 0xffffffffull);
@@ -3834,42 +3897,43 @@ static amvpt_status arena_reserve(DevArena &A, void *&buf, size_t &have, size_t 
     return AMVPT_OK;
 }
 
-static void launch_suffix_fused(bool tab, bool diff, int walk, dim3 grid, size_t lds, hipStream_t st, const KParams &P,
-                                const DScene *S, const Bufs &B) {
-#define AMVPT_FUSED(T_, D_)                                                                                           \
-    do {                                                                                                              \
-        if (walk == WALK_BRUTE_NS)                                                                                    \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_suffix_fused<T_, D_, WALK_BRUTE_NS>), grid, dim3(256), lds, st, P, S, B); \
-        else if (walk == WALK_BRUTE)                                                                                  \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_suffix_fused<T_, D_, WALK_BRUTE>), grid, dim3(256), lds, st, P, S, B); \
-    } while (0)
-    if (tab && diff) AMVPT_FUSED(true, true);
-    else if (tab) AMVPT_FUSED(true, false);
-    else if (diff) AMVPT_FUSED(false, true);
-    else AMVPT_FUSED(false, false);
-#undef AMVPT_FUSED
-}
+/* k_extend by (walk, binned rays; bin applies to the per-lane walks only) */
+static const Inst<scene_kernel> kExtend[] = {
+    AMVPT_INST(k_extend, WALK_LANE_TRI, true), AMVPT_INST(k_extend, WALK_LANE_NS, true), AMVPT_INST(k_extend, WALK_LANE, true),
+    AMVPT_INST(k_extend, WALK_BRUTE_NS, false), AMVPT_INST(k_extend, WALK_BRUTE, false), AMVPT_INST(k_extend, WALK_UNI, false),
+    AMVPT_INST(k_extend, WALK_LANE_TRI, false), AMVPT_INST(k_extend, WALK_LANE_NS, false), AMVPT_INST(k_extend, WALK_LANE, false)};
+/* k_bounce by (tables in LDS, all-diffuse, walk of the NEE ray traced in place: a brute-force one, else -1: k_shadow) */
+static const Inst<scene_kernel> kBounce[] = {
+    AMVPT_INST(k_bounce, true, true, WALK_BRUTE_NS), AMVPT_INST(k_bounce, true, true, WALK_BRUTE), AMVPT_INST(k_bounce, true, true, -1),
+    AMVPT_INST(k_bounce, true, false, WALK_BRUTE_NS), AMVPT_INST(k_bounce, true, false, WALK_BRUTE), AMVPT_INST(k_bounce, true, false, -1),
+    AMVPT_INST(k_bounce, false, true, WALK_BRUTE_NS), AMVPT_INST(k_bounce, false, true, WALK_BRUTE), AMVPT_INST(k_bounce, false, true, -1),
+    AMVPT_INST(k_bounce, false, false, WALK_BRUTE_NS), AMVPT_INST(k_bounce, false, false, WALK_BRUTE), AMVPT_INST(k_bounce, false, false, -1)};
+/* k_suffix_fused by (tables in LDS, all-diffuse, brute-force walk) */
+static const Inst<scene_kernel> kSuffixFused[] = {
+    AMVPT_INST(k_suffix_fused, true, true, WALK_BRUTE_NS), AMVPT_INST(k_suffix_fused, true, true, WALK_BRUTE),
+    AMVPT_INST(k_suffix_fused, true, false, WALK_BRUTE_NS), AMVPT_INST(k_suffix_fused, true, false, WALK_BRUTE),
+    AMVPT_INST(k_suffix_fused, false, true, WALK_BRUTE_NS), AMVPT_INST(k_suffix_fused, false, true, WALK_BRUTE),
+    AMVPT_INST(k_suffix_fused, false, false, WALK_BRUTE_NS), AMVPT_INST(k_suffix_fused, false, false, WALK_BRUTE)};
+/* k_bin_sort by (NEE rays, keys computed from the rays: the first depth's extension rays) */
+static const Inst<lane_kernel> kBinSort[] = {
+    AMVPT_INST(k_bin_sort, false, true), AMVPT_INST(k_bin_sort, false, false), AMVPT_INST(k_bin_sort, true, false)};
+/* k_splat_single (G = 1) and k_splat_adapt (the adaptive fill) by (C, filter form: FK_ANY for tent, Mitchell,
+ * Catmull-Rom and Lanczos, fixed-point film) */
+struct SplatLane {
+    lane_kernel single, adapt;
+    explicit operator bool() const { return single != nullptr; }
+};
+#define AMVPT_INST_SPLAT_LANE(...) {{__VA_ARGS__}, {k_splat_single<__VA_ARGS__>, k_splat_adapt<__VA_ARGS__>}}
+static const Inst<SplatLane> kSplatLane[] = {
+    AMVPT_INST_SPLAT_LANE(5, FK_ANY, true), AMVPT_INST_SPLAT_LANE(4, FK_ANY, true),
+    AMVPT_INST_SPLAT_LANE(5, FK_LEGACY, true), AMVPT_INST_SPLAT_LANE(4, FK_LEGACY, true),
+    AMVPT_INST_SPLAT_LANE(5, FK_ANY, false), AMVPT_INST_SPLAT_LANE(4, FK_ANY, false),
+    AMVPT_INST_SPLAT_LANE(5, FK_LEGACY, false), AMVPT_INST_SPLAT_LANE(4, FK_LEGACY, false)};
+#undef AMVPT_INST_SPLAT_LANE
 
-static void launch_bounce(bool tab, bool diff, int nee_walk, dim3 grid, size_t lds, hipStream_t st, const KParams &P,
-                          const DScene *S, const Bufs &B) {
-#define AMVPT_BOUNCE(T_, D_, N_) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bounce<T_, D_, N_>), grid, dim3(256), lds, st, P, S, B)
-#define AMVPT_BOUNCE_N(T_, D_)                                            \
-    do {                                                                 \
-        if (nee_walk == WALK_BRUTE_NS) AMVPT_BOUNCE(T_, D_, WALK_BRUTE_NS); \
-        else if (nee_walk == WALK_BRUTE) AMVPT_BOUNCE(T_, D_, WALK_BRUTE);  \
-        else AMVPT_BOUNCE(T_, D_, -1);                                    \
-    } while (0)
-    if (tab && diff) AMVPT_BOUNCE_N(true, true);
-    else if (tab) AMVPT_BOUNCE_N(true, false);
-    else if (diff) AMVPT_BOUNCE_N(false, true);
-    else AMVPT_BOUNCE_N(false, false);
-#undef AMVPT_BOUNCE_N
-#undef AMVPT_BOUNCE
-}
-
-typedef void (*primary_fn)(uint32_t, size_t, size_t, hipStream_t, const KParams &, const DScene *, const DView *,
-                           const Bufs &, bool, bool, bool, KTimer &);
-typedef void (*splat_fn)(dim3, hipStream_t, const KParams &, const DView *, const Bufs &, bool);
+typedef amvpt_status (*primary_fn)(uint32_t, size_t, size_t, hipStream_t, const KParams &, const DScene *, const DView *,
+                                   const Bufs &, bool, bool, bool, KTimer &);
+typedef amvpt_status (*splat_fn)(dim3, hipStream_t, const KParams &, const DView *, const Bufs &, bool);
 /* group sizes 2..16: the per-view bit masks (k_prim_req's request bits below the view index at
  * bit 16, k_mv_primary's valid / indirect flags at bits k and 16 + k) hold 16 views; entry 0 is
  * the runtime instance for 17..256 views (256-bit masks in vreq_w / lmask_w), entry 1 the one for
@@ -3900,9 +3964,8 @@ static uint32_t dispatch_g(uint32_t G) { return G > kMaxGWide ? 1u : G > kMaxG ?
  */
 constexpr uint32_t kSelTile = 256 * 16;
 constexpr unsigned long long kSelAgg = 1ull << 62, kSelInc = 2ull << 62, kSelVal = kSelAgg - 1;
-AMVPT_TU_LOCAL __global__ void __launch_bounds__(256) k_select_flagged(const uint8_t *amask, uint64_t n, uint32_t *out,
-                                                                      uint32_t *count, unsigned long long *status,
-                                                                      uint32_t *ticket, uint32_t n_tiles) {
+__global__ void __launch_bounds__(256) k_select_flagged(const uint8_t *amask, uint64_t n, uint32_t *out, uint32_t *count,
+                                                        unsigned long long *status, uint32_t *ticket, uint32_t n_tiles) {
     __shared__ uint32_t s_tile, s_wave[4];
     __shared__ unsigned long long s_prefix;
     if (threadIdx.x == 0) s_tile = atomicAdd(ticket, 1u);
@@ -3974,7 +4037,7 @@ AMVPT_TU_LOCAL __global__ void __launch_bounds__(256) k_select_flagged(const uin
 }
 
 /* adaptive fill: flagged lanes of each run of a rectangular lane set (one block per run) */
-AMVPT_TU_LOCAL __global__ void __launch_bounds__(256) k_run_counts(const uint8_t *amask, uint32_t run_len, uint32_t *counts) {
+__global__ void __launch_bounds__(256) k_run_counts(const uint8_t *amask, uint32_t run_len, uint32_t *counts) {
     __shared__ unsigned long long part[4];
     const uint8_t *m = amask + (size_t) blockIdx.x * run_len;
     unsigned long long c = 0;
@@ -3986,26 +4049,59 @@ AMVPT_TU_LOCAL __global__ void __launch_bounds__(256) k_run_counts(const uint8_t
 }
 
 /* deterministic mode: film += fixed-point sums (one thread per float, a fixed conversion per cell) */
-AMVPT_TU_LOCAL __global__ void k_fixed_resolve(float *film, const unsigned long long *fx, uint64_t n) {
+__global__ void k_fixed_resolve(float *film, const unsigned long long *fx, uint64_t n) {
     const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     film[i] = fixed_resolve_value((int64_t) fx[i], film[i], 1);
 }
 
-amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const amvpt_params *params,
-                         const amvpt_lane_set &lanes, const amvpt_film_window &fwin, void *stream,
-                         const amvpt_render_opts &opts, amvpt_counters *counters, float *records,
-                         uint32_t record_pass, bool fixed_film) {
-    /* fixed_film (amvpt_render_fixed): fwin.film is the caller's 32.32 integer window and fwin.overflow its integer
-     * list; `film` then only stands for the window's base address (film_fx index = film float index) */
-    float *const film = fwin.film;
-    if (!scene || !views || !params || !film) { set_error("amvpt_render: null argument"); return AMVPT_ERR_INVALID; }
-    RoctxScope range_render("amvpt_render");
-    const amvpt_params &Pp = *params;
-    hipStream_t st = (hipStream_t) stream;
-    const bool diffuse_spec = !(opts.flags & AMVPT_OPT_GENERIC_KERNELS);
-    const uint32_t trav = opts.traversal;
-    if (trav > 2) { set_error("amvpt_render: traversal must be 0 (auto), 1 (wave-uniform) or 2 (per-lane)"); return AMVPT_ERR_INVALID; }
+/* one amvpt_render call's arguments */
+struct RenderCall {
+    amvpt_scene *scene; const amvpt_view_desc *views; const amvpt_params &Pp; const amvpt_lane_set &lanes;
+    const amvpt_film_window &fwin; hipStream_t st; const amvpt_render_opts &opts; amvpt_counters *counters;
+    float *records; uint32_t record_pass;
+    /* amvpt_render_fixed: fwin.film is the caller's 32.32 integer window and fwin.overflow its integer list; the
+     * film pointer then only stands for the window's base address (film_fx index = film float index) */
+    bool fixed_film;
+};
+
+/* What a render does, decided from the call alone, without a device call (make_plan) */
+struct RenderPlan {
+    uint32_t spp_pp, n_passes, G, n_adapt;
+    bool is_mv, rng_carry;   /* rng_carry: the stock path's passes continue each lane's sampler (rng_in / rng_out) */
+    /* lane set: contiguous from lane_begin, or a pixel rectangle at (rx0, ry0) (n_runs runs of pixel rows); span
+     * lanes (virtual indices); partial: not the whole pass */
+    bool rect, partial;
+    uint64_t lane_begin, span;
+    uint32_t rx0, ry0, n_runs;
+    /* the splats add into a fixed-point film (deterministic): the caller's, or a private one resolved into the
+     * float film (private_fx) */
+    bool whole_film, private_fx, deterministic, do_fill;
+    size_t film_floats;
+    bool wide, diff_rec, vs_global;   /* runtime group-size instances; kDiff instances, compact view records; the
+                                       * runtime instance's per-view state in a global plane per lane (else LDS) */
+    int mplanes;                      /* uint4 planes per view mask of the runtime instances */
+    size_t per_lane;                  /* arena bytes per lane of a chunk */
+    int walk;                         /* WALK_* of the suffix */
+    bool tab_b, tab_p, uni_coh, fuse_nee, fuse_suffix, lane_walk, bin_ext, bin_nee;
+    /* dynamic LDS: k_bounce's tables, k_suffix_fused's box triangles, a staged BVH (k_prim_hit, k_vis), the same
+     * plus the two-box walks' stacks (k_extend, k_shadow), the primary shading's tables and views */
+    size_t lds_bounce, box_lds, lds_ext, lds_walk2, lds_prim;
+    uint32_t max_bounces;
+    /* the suffix's and the per-lane splats' instances (null: a kernel this render does not launch) */
+    scene_kernel extend, bounce, suffix_fused;
+    lane_kernel bin_rays, bin_paths, bin_nee_rays;
+    SplatLane splat;
+    KParams P;   /* every field that depends on neither an arena pointer nor the pass or chunk */
+};
+
+/* the boundary's argument checks, the passes, the lane set and the film window */
+static amvpt_status plan_lanes(const RenderCall &c, RenderPlan &pl) {
+    const amvpt_params &Pp = c.Pp;
+    const amvpt_lane_set &lanes = c.lanes;
+    const amvpt_film_window &fwin = c.fwin;
+    KParams &P = pl.P;
+    if (c.opts.traversal > 2) { set_error("amvpt_render: traversal must be 0 (auto), 1 (wave-uniform) or 2 (per-lane)"); return AMVPT_ERR_INVALID; }
     if (Pp.n_views == 0) { set_error("amvpt_render: n_views == 0"); return AMVPT_ERR_INVALID; }
     if (Pp.rfilter > AMVPT_RFILTER_LANCZOS) { set_error("amvpt_render: unknown rfilter " + std::to_string(Pp.rfilter)); return AMVPT_ERR_INVALID; }
     if (Pp.multisensor && !Pp.batch && Pp.n_views != Pp.grid_x * Pp.grid_y) {
@@ -4016,31 +4112,31 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
         set_error("amvpt_render: a batch MultiSensor needs grid_x == n_views and grid_y == 1");
         return AMVPT_ERR_INVALID;
     }
-    uint32_t spp, spp_pp, n_passes;
+    uint32_t spp, spp_pp;
     uint64_t L;
-    plan(Pp, spp, spp_pp, n_passes, L);
-    const bool is_mv = Pp.integrator == AMVPT_INTEGRATOR_MVPATH;
-    const bool reuse = is_mv && Pp.sa_reuse && Pp.n_views > 1 && Pp.reuse_count != 1;
-    const uint32_t G = reuse ? group_size(Pp) : 1;
-    if (G > kMaxGHuge) { set_error("amvpt_render: group size > 1024 not implemented"); return AMVPT_ERR_UNSUPPORTED; }
-    const uint32_t n_adapt = reuse ? std::min(Pp.adaptive, G - 1) : 0;
-    if (!is_mv && Pp.spp_pass_lim && (Pp.spp ? Pp.spp : 1) % std::min(Pp.spp_pass_lim, Pp.spp ? Pp.spp : 1u)) {
+    plan(Pp, spp, spp_pp, pl.n_passes, L);
+    pl.spp_pp = spp_pp;
+    pl.is_mv = Pp.integrator == AMVPT_INTEGRATOR_MVPATH;
+    const bool reuse = pl.is_mv && Pp.sa_reuse && Pp.n_views > 1 && Pp.reuse_count != 1;
+    pl.G = reuse ? group_size(Pp) : 1;
+    if (pl.G > kMaxGHuge) { set_error("amvpt_render: group size > 1024 not implemented"); return AMVPT_ERR_UNSUPPORTED; }
+    pl.n_adapt = reuse ? std::min(Pp.adaptive, pl.G - 1) : 0;
+    if (!pl.is_mv && Pp.spp_pass_lim && (Pp.spp ? Pp.spp : 1) % std::min(Pp.spp_pass_lim, Pp.spp ? Pp.spp : 1u)) {
         set_error("sample_count (" + std::to_string(Pp.spp ? Pp.spp : 1) + ") must be a multiple of spp_per_pass (" +
                   std::to_string(std::min(Pp.spp_pass_lim, Pp.spp ? Pp.spp : 1u)) + ").");
         return AMVPT_ERR_INVALID;
     }
-    /* the stock path's passes continue each lane's sampler (rng_in / rng_out) */
-    const bool rng_carry = !is_mv && n_passes > 1;
+    pl.rng_carry = !pl.is_mv && pl.n_passes > 1;
     if (Pp.multisensor && (Pp.grid_x == 0 || Pp.grid_y == 0 || Pp.film_width % Pp.grid_x || Pp.film_height % Pp.grid_y)) {
         set_error("Film size must be divisible by grid dimensions !");
         return AMVPT_ERR_INVALID;
     }
     for (uint32_t v = 0; v < Pp.n_views; ++v)
-        if (views[v].type != AMVPT_CAMERA_PERSPECTIVE && views[v].type != AMVPT_CAMERA_THINLENS) {
+        if (c.views[v].type != AMVPT_CAMERA_PERSPECTIVE && c.views[v].type != AMVPT_CAMERA_THINLENS) {
             set_error("amvpt_render: unknown camera type");
             return AMVPT_ERR_INVALID;
         }
-    /* ---- lane set: contiguous [lane_begin, lane_end), or a pixel rectangle (runs of pixel rows) ---- */
+    /* ---- lane set ---- */
     const uint32_t QW = Pp.film_width, QH = Pp.film_height;
     bool rect = lanes.rect_width != 0;
     uint64_t lane_begin = lanes.lane_begin, lane_end = lanes.lane_end;
@@ -4062,52 +4158,49 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
         }
     }
     if (!rect && lane_end > L) lane_end = L;
-    const uint64_t span = lane_begin < lane_end ? lane_end - lane_begin : 0;
-    const uint32_t n_runs = span == 0 ? 0u : (rect ? rh : 1u);
+    pl.rect = rect; pl.lane_begin = lane_begin; pl.rx0 = rx0; pl.ry0 = ry0;
+    pl.span = lane_begin < lane_end ? lane_end - lane_begin : 0;
+    pl.n_runs = pl.span == 0 ? 0u : (rect ? rh : 1u);
+    P.range_begin = rect ? 0 : lane_begin;
+    P.rect = rect ? 1u : 0u;
+    P.rect_x0 = rx0; P.rect_y0 = ry0;
+    P.run_len = rect ? rw * spp_pp : 0u;
     /* ---- film window ---- */
     if ((uint64_t) fwin.x0 + fwin.width > QW || (uint64_t) fwin.y0 + fwin.height > QH) {
         set_error("amvpt_render: film window outside the quilt");
         return AMVPT_ERR_INVALID;
     }
-    const bool whole_film = fwin.x0 == 0 && fwin.y0 == 0 && fwin.width == QW && fwin.height == QH;
-    /* the splats add into a fixed-point film: the caller's, or (the flag) a private one resolved into the float film */
-    const bool private_fx = !fixed_film && (opts.flags & AMVPT_OPT_DETERMINISTIC) != 0;
-    const bool deterministic = fixed_film || private_fx;
-    if (private_fx && !whole_film) {
+    pl.whole_film = fwin.x0 == 0 && fwin.y0 == 0 && fwin.width == QW && fwin.height == QH;
+    pl.private_fx = !c.fixed_film && (c.opts.flags & AMVPT_OPT_DETERMINISTIC) != 0;
+    pl.deterministic = c.fixed_film || pl.private_fx;
+    pl.film_floats = (size_t) QW * QH * (Pp.film_alpha ? 5 : 4);
+    if (pl.private_fx && !pl.whole_film) {
         set_error("amvpt_render: AMVPT_OPT_DETERMINISTIC needs a whole-quilt film window");
         return AMVPT_ERR_UNSUPPORTED;
     }
-    if (!whole_film && !fwin.overflow) {
+    if (!pl.whole_film && !fwin.overflow) {
         set_error("amvpt_render: a film window smaller than the quilt needs an overflow list");
         return AMVPT_ERR_INVALID;
     }
     /* the adaptive fill compacts the whole pass (its RNG seeds depend on the global
      * wavefront): a partial lane set needs the host's count exchange */
-    const bool do_fill = n_adapt && !Pp.debug;
-    const bool partial = rect || lane_begin != 0 || lane_end != L;
-    const amvpt_run_exchange_fn exchange = opts.exchange;
-    void *const exchange_ctx = opts.exchange_ctx;
-    if (do_fill && partial && !exchange) {
+    pl.do_fill = pl.n_adapt && !Pp.debug;
+    pl.partial = rect || lane_begin != 0 || lane_end != L;
+    if (pl.do_fill && pl.partial && !c.opts.exchange) {
         set_error("amvpt_render: adaptive > 0 over a lane range needs amvpt_set_adaptive_exchange "
                   "(or the whole frame: lane_begin = 0, lane_end = all lanes)");
         return AMVPT_ERR_UNSUPPORTED;
     }
-    if (span == 0) {
-        /* an empty lane set still takes part in every pass's count exchange (an all-gather on
-         * the host side: the other ranks would wait for it forever) */
-        if (do_fill && partial)
-            for (uint32_t pass = 0; pass < n_passes; ++pass) {
-                uint64_t total = 0;
-                if (exchange(exchange_ctx, 0, nullptr, nullptr, nullptr, &total) != 0) {
-                    set_error("amvpt_render: adaptive count exchange failed");
-                    return AMVPT_ERR_INVALID;
-                }
-            }
-        if (counters) *counters = amvpt_counters{};
-        return AMVPT_OK;
-    }
+    return AMVPT_OK;
+}
 
-    KParams P{};
+/* the kernel parameters the call decides */
+static void plan_params(const RenderCall &c, RenderPlan &pl) {
+    const amvpt_params &Pp = c.Pp;
+    const amvpt_scene *scene = c.scene;
+    const amvpt_film_window &fwin = c.fwin;
+    const uint32_t spp_pp = pl.spp_pp, QW = Pp.film_width;
+    KParams &P = pl.P;
     P.W = Pp.film_width; P.H = Pp.film_height; P.C = Pp.film_alpha ? 5 : 4;
     P.spp_pp = spp_pp;
     uint32_t log_spp = 0;
@@ -4115,13 +4208,13 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
     P.log_spp = log_spp;
     P.pow2 = (1u << log_spp) == spp_pp;
     P.max_depth = Pp.max_depth; P.rr_depth = Pp.rr_depth;
-    P.sa_mis = Pp.sa_mis; P.fast_mis = Pp.fast_mis; P.debug = Pp.debug; P.n_adapt = n_adapt;
-    P.G = G;
+    P.sa_mis = Pp.sa_mis; P.fast_mis = Pp.fast_mis; P.debug = Pp.debug; P.n_adapt = pl.n_adapt;
+    P.G = pl.G;
     P.multisensor = Pp.multisensor; P.batch = Pp.batch; P.n_views = Pp.n_views;
     /* grid: its first sub-sensor decides (grid.cpp:228); batch: any child (batch.cpp:127) */
     P.needs_ap = 0;
     for (uint32_t v = 0; v < (Pp.multisensor && Pp.batch ? Pp.n_views : 1u); ++v)
-        P.needs_ap |= views[v].type == AMVPT_CAMERA_THINLENS ? 1u : 0u;
+        P.needs_ap |= c.views[v].type == AMVPT_CAMERA_THINLENS ? 1u : 0u;
     P.gx = Pp.grid_x ? Pp.grid_x : 1; P.gy = Pp.grid_y ? Pp.grid_y : 1;
     P.rev_x = Pp.reverse_x; P.rev_y = Pp.reverse_y;
     /* quilt tile pitch of reprojected views: film->size() / grid (mvpath_multi.h:62), the full film */
@@ -4129,8 +4222,8 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
     P.sres_x = fullW / P.gx; P.sres_y = fullH / P.gy;
     P.box = Pp.rfilter == AMVPT_RFILTER_BOX;
     P.coalesce_single = spp_pp >= 4;
-    P.path_box_pos = (!is_mv && P.box) ? 1 : 0;
-    P.is_mvpath = is_mv;
+    P.path_box_pos = (!pl.is_mv && P.box) ? 1 : 0;
+    P.is_mvpath = pl.is_mv;
     P.inv_w = 1.f / (float) P.W;
     P.inv_h = 1.f / (float) P.H;
     P.off_x = Pp.crop_offset_x; P.off_y = Pp.crop_offset_y;
@@ -4138,10 +4231,10 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
     P.adj_oy = -(float) P.off_y * P.inv_h;
     P.nc_ox = (float) (-(int) P.off_x) - .5f;
     P.nc_oy = (float) (-(int) P.off_y) - .5f;
-    P.adapt_w = 1.f / (float) (n_adapt + 1);
-    P.trav_mode = trav;
-    P.box_screen = (opts.flags & AMVPT_OPT_NO_BOX_SCREEN) ? 0u : 1u;
-    P.split_prim = (opts.flags & AMVPT_OPT_SPLIT_PRIMARY) ? 1u : 0u;
+    P.adapt_w = 1.f / (float) (pl.n_adapt + 1);
+    P.trav_mode = c.opts.traversal;
+    P.box_screen = (c.opts.flags & AMVPT_OPT_NO_BOX_SCREEN) ? 0u : 1u;
+    P.split_prim = (c.opts.flags & AMVPT_OPT_SPLIT_PRIMARY) ? 1u : 0u;
     for (int a = 0; a < 3; ++a) {
         const float ext = scene->root_hi[a] - scene->root_lo[a];
         P.bin_lo[a] = scene->root_lo[a];
@@ -4149,47 +4242,126 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
     }
     P.sph = !scene->has_spheres ? 0u : scene->n_sph <= 64u ? 2u : 1u;
     P.win_rs = AMVPT_WIN_RS;
-    P.range_begin = rect ? 0 : lane_begin;
-    P.rect = rect ? 1u : 0u;
-    P.rect_x0 = rx0; P.rect_y0 = ry0;
-    P.run_len = rect ? rw * spp_pp : 0u;
     P.fx0 = fwin.x0; P.fy0 = fwin.y0; P.fw = fwin.width; P.fh = fwin.height;
-    P.overflow = whole_film ? nullptr : fwin.overflow;
-    P.ov_cap = whole_film ? 0 : fwin.overflow_capacity;
-    /* the list's count before this render: renders append (amvpt_film_window), film_overflow reports the
-     * cells this one added */
-    uint64_t overflow_before = 0, overflow_added = 0;
-    if (P.overflow) {
-        HIPCHK(hipMemcpyAsync(&overflow_before, P.overflow, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
+    P.overflow = pl.whole_film ? nullptr : fwin.overflow;
+    P.ov_cap = pl.whole_film ? 0 : fwin.overflow_capacity;
     P.valid_ray0 = (!Pp.hide_emitters && scene->dev.environment >= 0) ? 1u : 0u;
     /* row-reduced splat (row_put): RGBW film, >= 16 samples per pixel and pass (a 16-lane row = one pixel), and a
      * filter whose scalars are literals in the row kernels (default_filter, filter_eval_lit; checked bit for bit by
      * filter_setup): the default Gaussian in every render, tent of radius 1, Mitchell at B = C = 1/3 and Catmull-Rom
      * in plain multi-view renders (whole-quilt film, no records, no debug: the instances launch_splat has for them).
      * AMVPT_OPT_BLOCK_SPLAT keeps the per-lane block window */
-    {
-        bool literal = false;
-        filter_setup(Pp, P.filt, P.filt_kind, &literal);
-        const bool has_row = P.filt_kind == FILT_GAUSSIAN ||
-                             ((P.filt_kind == FILT_TENT || P.filt_kind == FILT_MITCHELL || P.filt_kind == FILT_CATMULLROM) &&
-                              G > 1 && whole_film && !records && !Pp.debug && !deterministic);
-        P.row_splat = (!(opts.flags & AMVPT_OPT_BLOCK_SPLAT) && P.C == 4 && literal && has_row && P.pow2 &&
-                       spp_pp >= 16) ? 1u : 0u;
-    }
+    bool literal = false;
+    filter_setup(Pp, P.filt, P.filt_kind, &literal);
+    const bool has_row = P.filt_kind == FILT_GAUSSIAN ||
+                         ((P.filt_kind == FILT_TENT || P.filt_kind == FILT_MITCHELL || P.filt_kind == FILT_CATMULLROM) &&
+                          pl.G > 1 && pl.whole_film && !c.records && !Pp.debug && !pl.deterministic);
+    P.row_splat = (!(c.opts.flags & AMVPT_OPT_BLOCK_SPLAT) && P.C == 4 && literal && has_row && P.pow2 &&
+                   spp_pp >= 16) ? 1u : 0u;
     /* tiled slots: whole 4-row bands of a quilt row width divisible by 4, 16 samples per pixel and pass,
-     * contiguous lane sets whose chunks start and end on band boundaries */
-    {
-        const uint64_t band = 4ull * QW * 16ull;
-        P.tile_w = (P.row_splat && spp_pp == 16 && QW % 4 == 0 && !rect && lane_begin % band == 0 &&
-                    span % band == 0 && span <= 0xffffffffull) ? QW : 0u;
-    }
+     * contiguous lane sets whose chunks start and end on band boundaries (render_impl checks the chunk) */
+    const uint64_t band = 4ull * QW * 16ull;
+    P.tile_w = (P.row_splat && spp_pp == 16 && QW % 4 == 0 && !pl.rect && pl.lane_begin % band == 0 &&
+                pl.span % band == 0 && pl.span <= 0xffffffffull) ? QW : 0u;
+    if (pl.deterministic) P.fx_direct = (c.opts.flags & AMVPT_OPT_FIXED_DIRECT) ? 1u : 0u;
+}
 
-    /* views to device (tiny) */
-    std::vector<DView> hv(Pp.n_views);
-    for (uint32_t v = 0; v < Pp.n_views; ++v) {
-        const amvpt_view_desc &d = views[v];
+/* the walk tier, the buffers a lane needs and the kernels' dynamic LDS */
+static void plan_walks(const RenderCall &c, RenderPlan &pl) {
+    const amvpt_params &Pp = c.Pp;
+    const amvpt_scene *scene = c.scene;
+    const amvpt_render_opts &opts = c.opts;
+    const uint32_t trav = opts.traversal, G = pl.G;
+    /* lane arena: queues (2 x 5 x 16 B), lane_out + hit (32 B), NEE queue (52 B), visibility requests
+     * (48 B), lane records (64 B), view records (4 B x G all-diffuse, else 32 B x G), ballots (G / 8 B) */
+    pl.wide = G > kMaxG;
+    pl.mplanes = G > kMaxGWide ? mask_planes<-1>() : mask_planes<0>();
+    pl.diff_rec = scene->all_diffuse && !(opts.flags & AMVPT_OPT_GENERIC_KERNELS) && !pl.wide;
+    /* the runtime instance's per-view state: LDS (64-thread blocks) while it fits, else a global
+     * VS_FIELDS x G float plane per lane */
+    pl.tab_b = tables_staged(scene->dev, 0);
+    pl.tab_p = tables_staged(scene->dev, Pp.n_views);
+    pl.lds_prim = pl.tab_p ? scene->dev.tab_bytes + views_lds_bytes(Pp.n_views) : 0u;
+    pl.vs_global = pl.wide && pl.lds_prim + (size_t) VS_FIELDS * G * 64 * sizeof(float) > 65536;
+    pl.per_lane = 2 * kQPlanes * 16 + 32 + 52 + 48 + 64 + 32 + 8 + 6 /* binned rays, binned NEE results, keys */ +
+                  (size_t) (pl.diff_rec ? 4 : 36) * G + (G + 7) / 8 +
+                  (pl.wide ? (size_t) 4 * 16 * pl.mplanes : 0) + (pl.vs_global ? (size_t) VS_FIELDS * 4 * G : 0);
+    const bool uni = scene_uniform(scene->dev.n_nodes, trav);
+    /* the coherent primary and visibility rays walk wave-uniformly on every BVH in automatic mode
+     * (see launch_primary); the incoherent suffix rays keep the per-lane walk */
+    pl.uni_coh = uni || trav == 0u;
+    /* suffix walk: brute force for tiny scenes in auto mode */
+    pl.walk = uni ? WALK_UNI : scene->has_spheres ? WALK_LANE : scene->bvh_tri_only ? WALK_LANE_TRI : WALK_LANE_NS;
+    if (uni && trav == 0u && scene->dev.n_prims <= kBrutePrims) pl.walk = scene->has_spheres ? WALK_BRUTE : WALK_BRUTE_NS;
+    /* NEE traced inside k_bounce (brute-force walks; AMVPT_OPT_SPLIT_NEE keeps k_shadow) */
+    pl.fuse_nee = (pl.walk == WALK_BRUTE || pl.walk == WALK_BRUTE_NS) && !(opts.flags & AMVPT_OPT_SPLIT_NEE);
+    /* the whole suffix in one launch, paths in registers (brute-force walks with fused NEE;
+     * AMVPT_OPT_WAVEFRONT_SUFFIX keeps the per-depth k_extend / k_bounce wavefronts) */
+    pl.fuse_suffix = pl.fuse_nee && !(opts.flags & AMVPT_OPT_WAVEFRONT_SUFFIX);
+    /* ray binning (k_bin_sort) for the per-lane suffix walks of BVHs read from device memory */
+    pl.lds_ext = scene_lds_bytes(scene->dev, trav);
+    pl.lane_walk = is_lane_walk(pl.walk) && !pl.fuse_suffix && pl.lds_ext == 0u;
+    pl.bin_ext = pl.lane_walk && !(opts.flags & AMVPT_OPT_NO_BINNING);   /* the extension rays (k_extend) */
+    pl.bin_nee = pl.bin_ext && !pl.fuse_nee;                              /* the NEE rays (k_shadow) */
+    pl.lds_bounce = pl.tab_b ? scene->dev.tab_bytes : 0u;
+    pl.box_lds = pl.P.box_screen ? (size_t) scene->n_boxes * 12u * sizeof(DPrim) : 0u;   /* staged for box_walk */
+    /* the two-box BVH walks (DScene::nodes2) for the per-lane suffix walks of BVHs read from device memory: a stack
+     * of kStack2 u32 entries per thread after the kernels' other LDS (AMVPT_OPT_THREADED_BVH keeps the threaded walks) */
+    KParams &P = pl.P;
+    P.bvh2 = (scene->n_nodes2 && pl.lane_walk && !(opts.flags & AMVPT_OPT_THREADED_BVH)) ? 1u : 0u;
+    P.stk_off_ext = P.stk_off_any = (uint32_t) ((pl.lds_ext + 15u) & ~(size_t) 15u);
+    pl.lds_walk2 = P.bvh2 ? P.stk_off_ext + (size_t) kStack2 * kStk2Stride * 4u : pl.lds_ext;
+    pl.max_bounces = P.max_depth == 0xffffffffu ? 0xffffffffu : P.max_depth + 1;
+}
+
+/* which instances of the main unit's families the render launches */
+static amvpt_status plan_kernels(RenderPlan &pl) {
+    const KParams &P = pl.P;
+    const bool brute = pl.walk == WALK_BRUTE || pl.walk == WALK_BRUTE_NS;
+    amvpt_status s = AMVPT_OK;
+    pl.extend = pl.bounce = pl.suffix_fused = nullptr;
+    pl.bin_rays = pl.bin_paths = pl.bin_nee_rays = nullptr;
+    if (pl.fuse_suffix) {
+        if ((s = find_inst("k_suffix_fused", kSuffixFused, {pl.tab_b, pl.diff_rec, pl.walk}, pl.suffix_fused)) != AMVPT_OK) return s;
+    } else {
+        if ((s = find_inst("k_extend", kExtend, {pl.walk, pl.bin_ext && is_lane_walk(pl.walk)}, pl.extend)) != AMVPT_OK) return s;
+        if ((s = find_inst("k_bounce", kBounce, {pl.tab_b, pl.diff_rec, pl.fuse_nee && brute ? pl.walk : -1}, pl.bounce)) != AMVPT_OK) return s;
+        if (pl.bin_ext && (s = find_inst("k_bin_sort", kBinSort, {false, true}, pl.bin_rays)) != AMVPT_OK) return s;
+        if (pl.bin_ext && (s = find_inst("k_bin_sort", kBinSort, {false, false}, pl.bin_paths)) != AMVPT_OK) return s;
+        if (pl.bin_nee && (s = find_inst("k_bin_sort", kBinSort, {true, false}, pl.bin_nee_rays)) != AMVPT_OK) return s;
+    }
+    return find_inst("k_splat_single / k_splat_adapt", kSplatLane,
+                     {P.C == 5 ? 5 : 4, P.filt_kind > FILT_GAUSSIAN ? FK_ANY : FK_LEGACY, pl.deterministic}, pl.splat);
+}
+
+static amvpt_status make_plan(const RenderCall &c, RenderPlan &pl) {
+    pl.P = KParams{};
+    const amvpt_status s = plan_lanes(c, pl);
+    if (s != AMVPT_OK) return s;
+    plan_params(c, pl);
+    plan_walks(c, pl);
+    return plan_kernels(pl);
+}
+
+/* an empty lane set still takes part in every pass's count exchange (an all-gather on the host side: the other
+ * ranks would wait for it forever) */
+static amvpt_status render_nothing(const RenderCall &c, const RenderPlan &pl) {
+    if (pl.do_fill && pl.partial)
+        for (uint32_t pass = 0; pass < pl.n_passes; ++pass) {
+            uint64_t total = 0;
+            if (c.opts.exchange(c.opts.exchange_ctx, 0, nullptr, nullptr, nullptr, &total) != 0) {
+                set_error("amvpt_render: adaptive count exchange failed");
+                return AMVPT_ERR_INVALID;
+            }
+        }
+    if (c.counters) *c.counters = amvpt_counters{};
+    return AMVPT_OK;
+}
+
+static std::vector<DView> host_views(const RenderCall &c) {
+    std::vector<DView> hv(c.Pp.n_views);
+    for (uint32_t v = 0; v < c.Pp.n_views; ++v) {
+        const amvpt_view_desc &d = c.views[v];
         DView &o = hv[v];
         std::memcpy(o.to_world, d.to_world, 12 * sizeof(float));
         std::memcpy(o.to_world_inv, d.to_world_inv, 12 * sizeof(float));
@@ -4203,117 +4375,91 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
         o.focus_distance = d.focus_distance;
         o.pad1 = 0.f;
     }
+    return hv;
+}
 
-    /* lane arena: queues (2 x 5 x 16 B), lane_out + hit (32 B), NEE queue (52 B), visibility requests
-     * (48 B), lane records (64 B), view records (4 B x G all-diffuse, else 32 B x G), ballots (G / 8 B) */
-    const bool wide = G > kMaxG;   /* the runtime group-size instances (256- / 1024-bit view masks) */
-    const int mplanes = G > kMaxGWide ? mask_planes<-1>() : mask_planes<0>();   /* uint4 planes per mask */
-    const bool diff_rec = scene->all_diffuse && diffuse_spec && !wide;   /* kDiff instances, compact view records */
-    /* the runtime instance's per-view state: LDS (64-thread blocks) while it fits, else a global
-     * VS_FIELDS x G float plane per lane */
-    const size_t lds_tab_views = tables_staged(scene->dev, Pp.n_views)
-                                     ? scene->dev.tab_bytes + views_lds_bytes(Pp.n_views) : 0u;
-    const bool vs_global = wide && lds_tab_views + (size_t) VS_FIELDS * G * 64 * sizeof(float) > 65536;
-    const size_t per_lane = 2 * kQPlanes * 16 + 32 + 52 + 48 + 64 + 32 + 8 + 6 /* binned rays, binned NEE results, keys */ +
-                            (size_t) (diff_rec ? 4 : 36) * G + (G + 7) / 8 +
-                            (wide ? (size_t) 4 * 16 * mplanes : 0) + (vs_global ? (size_t) VS_FIELDS * 4 * G : 0);
-    uint64_t chunk_max = opts.chunk_lanes ? std::max<uint64_t>(256, opts.chunk_lanes) : 0;
+/* every return of a render that holds the arena joins the side streams into the render stream and records `done`
+ * (also the error paths) */
+struct ArenaRelease {
+    DevArena &A; hipStream_t st; int n_side; bool side = false;
+    /* the side streams start after `st`'s work so far */
+    amvpt_status fork() {
+        if (n_side < 1 || side) return AMVPT_OK;
+        HIPCHK(hipEventRecord(A.fork, st));
+        for (int k = 0; k < n_side; ++k) HIPCHK(hipStreamWaitEvent(A.side[k], A.fork, 0));
+        side = true;
+        return AMVPT_OK;
+    }
+    void join() {
+        if (!side) return;
+        side = false;
+        for (int k = 0; k < n_side; ++k)
+            if (hipEventRecord(A.join[k], A.side[k]) == hipSuccess) (void) hipStreamWaitEvent(st, A.join[k], 0);
+    }
+    ~ArenaRelease() {
+        join();
+        if (hipEventRecord(A.done, st) == hipSuccess) { A.pending = true; A.last = st; }
+    }
+};
+
+constexpr size_t kStatsBytes = (size_t) kStats * kStatShards * 8, kCntBytes = (size_t) 3 * kQParts * kCntStride * 4;
+/* one partition holds the pushes of every kQParts-th producer block (<= 256 lanes each) */
+static uint32_t qcap_of(uint64_t c) { return (uint32_t) (((c + kQParts - 1) / kQParts + 512 + 63) & ~(uint64_t) 63); }
+static size_t set_bytes_of(const RenderPlan &pl, uint64_t c) {
+    return kCntBytes + pl.per_lane * std::max<uint64_t>(c, (uint64_t) qcap_of(c) * kQParts) + 8192;
+}
+/* Chunks of the per-depth wavefront suffix (BVH scenes) take turns over up to four buffer sets on as many streams
+ * (the render stream and the arena's side streams): one chunk's short deep-bounce launches and tails leave CUs idle
+ * that the other chunks' kernels fill (mesh 550 -> 599 Msamples/s with two, round 2; 967 -> 1001 with four, r05zi).
+ * The fused-suffix scenes gain 0.0-0.5 % (r03i) and keep one stream, so their per-kernel HIP-event times are not
+ * overlapped (AMVPT_OPT_ONE_STREAM forces one stream everywhere).  As many buffer sets as chunk streams, at most one
+ * per chunk of the render (chunk i on set i mod n across the passes) and 192 GB of sets in all */
+static int sets_for(const RenderCall &c, const RenderPlan &pl, uint64_t chunk) {
+    int n = (AMVPT_CHUNK_STREAMS > 1 && pl.span > chunk && !pl.fuse_suffix &&
+             !(c.opts.flags & AMVPT_OPT_ONE_STREAM)) ? std::min(AMVPT_CHUNK_STREAMS, kMaxChunkStreams) : 1;
+    n = (int) std::min<uint64_t>((uint64_t) n, (uint64_t) pl.n_passes * ((pl.span + chunk - 1) / chunk));
+    while (n > 2 && set_bytes_of(pl, chunk) * (size_t) n > (192ull << 30)) --n;
+    return n;
+}
+
+/* The chunk size and the number of buffer sets, with the lane arena reserved for them.
+ * Device-memory budget (ABI 10; the reference bounds a pass's memory with spp_pass_lim and its wavefront
+ * cap, mvpath.cpp:36-41,133-147): opts.budget_mib, else this device's free memory plus what the arena
+ * already holds, less max(2 GiB, 1/64 of the device).  Sizing drops chunk streams' buffer sets first, then
+ * halves the chunk (records and films do not depend on either); a failing allocation takes the same steps
+ * before the render reports AMVPT_ERR_OOM. */
+static amvpt_status size_arena(const RenderCall &c, const RenderPlan &pl, DevArena &A, size_t views_bytes,
+                               uint64_t &chunk, int &n_sets) {
+    const uint64_t span = pl.span;
+    uint64_t chunk_max = c.opts.chunk_lanes ? std::max<uint64_t>(256, c.opts.chunk_lanes) : 0;
     if (chunk_max == 0) {
         chunk_max = 1ull << 26;
-        while (chunk_max > (1ull << 16) && chunk_max * per_lane > (48ull << 30)) chunk_max >>= 1;
+        while (chunk_max > (1ull << 16) && chunk_max * pl.per_lane > (48ull << 30)) chunk_max >>= 1;
     }
-    uint64_t chunk = std::min<uint64_t>(chunk_max, span);
-    const size_t views_bytes = ((hv.size() * sizeof(DView)) + 255) & ~(size_t) 255;
-    /* one partition holds the pushes of every kQParts-th producer block (<= 256 lanes each) */
-    auto qcap_of = [](uint64_t c) { return (uint32_t) (((c + kQParts - 1) / kQParts + 512 + 63) & ~(uint64_t) 63); };
-    const size_t stats_bytes = (size_t) kStats * kStatShards * 8, cnt_bytes = (size_t) 3 * kQParts * kCntStride * 4;
-    const bool tab_b = tables_staged(scene->dev, 0), tab_p = tables_staged(scene->dev, Pp.n_views);
-    const bool uni = scene_uniform(scene->dev.n_nodes, trav);
-    /* the coherent primary and visibility rays walk wave-uniformly on every BVH in automatic mode
-     * (see launch_primary); the incoherent suffix rays keep the per-lane walk */
-    const bool uni_coh = uni || trav == 0u;
-    /* suffix walk: brute force for tiny scenes in auto mode */
-    int walk = uni ? WALK_UNI : scene->has_spheres ? WALK_LANE : scene->bvh_tri_only ? WALK_LANE_TRI : WALK_LANE_NS;
-    if (uni && trav == 0u && scene->dev.n_prims <= kBrutePrims) walk = scene->has_spheres ? WALK_BRUTE : WALK_BRUTE_NS;
-    const bool diff = diff_rec;                                                                           /* kDiff instances */
-    /* NEE traced inside k_bounce (brute-force walks; AMVPT_OPT_SPLIT_NEE keeps k_shadow) */
-    const bool fuse_nee = (walk == WALK_BRUTE || walk == WALK_BRUTE_NS) && !(opts.flags & AMVPT_OPT_SPLIT_NEE);
-    /* the whole suffix in one launch, paths in registers (brute-force walks with fused NEE;
-     * AMVPT_OPT_WAVEFRONT_SUFFIX keeps the per-depth k_extend / k_bounce wavefronts) */
-    const bool fuse_suffix = fuse_nee && !(opts.flags & AMVPT_OPT_WAVEFRONT_SUFFIX);
-    /* chunks of the per-depth wavefront suffix (BVH scenes) take turns over up to four buffer sets on as many
-     * streams (the render stream and the arena's side streams): one chunk's short deep-bounce launches and
-     * tails leave CUs idle that the other chunks' kernels fill (mesh 550 -> 599 Msamples/s with two, round 2;
-     * 967 -> 1001 with four, r05zi).  The
-     * fused-suffix scenes gain 0.0-0.5 % (r03i) and keep one stream, so their per-kernel HIP-event
-     * times are not overlapped (AMVPT_OPT_ONE_STREAM forces one stream everywhere) */
-    /* ray binning (k_bin_sort) for the per-lane suffix walks of BVHs read from device memory */
-    const bool lane_walk = (walk == WALK_LANE || walk == WALK_LANE_NS || walk == WALK_LANE_TRI) && !fuse_suffix && scene_lds_bytes(scene->dev, trav) == 0u;
-    const bool bin_ext = lane_walk && !(opts.flags & AMVPT_OPT_NO_BINNING);   /* the extension rays (k_extend) */
-    const bool bin_nee = bin_ext && !fuse_nee;                                 /* the NEE rays (k_shadow) */
-    auto set_bytes_of = [&](uint64_t c) {
-        return cnt_bytes + per_lane * std::max<uint64_t>(c, (uint64_t) qcap_of(c) * kQParts) + 8192;
-    };
-    /* as many buffer sets as chunk streams, at most one per chunk of the render (chunk i on set i mod n across
-     * the passes) and 192 GB of sets in all */
-    auto sets_for = [&](uint64_t c) {
-        int n = (AMVPT_CHUNK_STREAMS > 1 && span > c && !fuse_suffix &&
-                 !(opts.flags & AMVPT_OPT_ONE_STREAM)) ? std::min(AMVPT_CHUNK_STREAMS, kMaxChunkStreams) : 1;
-        n = (int) std::min<uint64_t>((uint64_t) n, (uint64_t) n_passes * ((span + c - 1) / c));
-        while (n > 2 && set_bytes_of(c) * (size_t) n > (192ull << 30)) --n;
-        return n;
-    };
-    int n_sets = sets_for(chunk);
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
-    DevArena &A = dev_arena(dev);
-    std::unique_lock<std::mutex> arena_lock(A.mu);
-    if (!A.done) HIPCHK(hipEventCreateWithFlags(&A.done, hipEventDisableTiming));
-    /* the previous render's buffers may still be in flight on another stream */
-    if (A.pending && A.last != st) HIPCHK(hipStreamWaitEvent(st, A.done, 0));
-    /* every return below joins the side streams into this one and records `done` (also the error paths) */
-    struct ArenaRelease {
-        DevArena &A; hipStream_t st; int n_side; bool side = false;
-        void join() {
-            if (!side) return;
-            side = false;
-            for (int k = 0; k < n_side; ++k)
-                if (hipEventRecord(A.join[k], A.side[k]) == hipSuccess) (void) hipStreamWaitEvent(st, A.join[k], 0);
-        }
-        ~ArenaRelease() {
-            join();
-            if (hipEventRecord(A.done, st) == hipSuccess) { A.pending = true; A.last = st; }
-        }
-    } arena_release{A, st, 0};
-    /* Device-memory budget (ABI 10; the reference bounds a pass's memory with spp_pass_lim and its wavefront
-     * cap, mvpath.cpp:36-41,133-147): opts.budget_mib, else this device's free memory plus what the arena
-     * already holds, less max(2 GiB, 1/64 of the device).  Sizing drops chunk streams' buffer sets first, then
-     * halves the chunk (records and films do not depend on either); a failing allocation takes the same steps
-     * before the render reports AMVPT_ERR_OOM. */
+    chunk = std::min<uint64_t>(chunk_max, span);
+    n_sets = sets_for(c, pl, chunk);
     const size_t held = A.bytes + A.abytes + A.fxbytes + A.cbytes;
     size_t budget = 0;
-    if (opts.budget_mib) {
-        budget = (size_t) opts.budget_mib << 20;
+    if (c.opts.budget_mib) {
+        budget = (size_t) c.opts.budget_mib << 20;
     } else {
         size_t fr = 0, tot = 0;
         HIPCHK(hipMemGetInfo(&fr, &tot));
         const size_t headroom = std::max<size_t>(2ull << 30, tot / 64);
         budget = fr + held > headroom ? fr + held - headroom : 0;
     }
-    /* the span-sized buffers below (deterministic film, sampler states, adaptive fill) */
-    const size_t other_need = (private_fx ? (size_t) QW * QH * (Pp.film_alpha ? 5 : 4) * 8 : 0) +
-                              (rng_carry ? (size_t) 16 * span : 0) + (do_fill ? (size_t) 6 * span + (1u << 20) : 0);
+    /* the span-sized buffers (deterministic film, sampler states, adaptive fill) */
+    const size_t other_need = (pl.private_fx ? pl.film_floats * 8 : 0) +
+                              (pl.rng_carry ? (size_t) 16 * span : 0) + (pl.do_fill ? (size_t) 6 * span + (1u << 20) : 0);
     const uint64_t min_chunk = std::min<uint64_t>(span, 1ull << 16);
-    auto need_of = [&](uint64_t c, int n) { return views_bytes + stats_bytes + set_bytes_of(c) * (size_t) n; };
     auto shrink = [&]() {   /* one step down: a buffer set less, then half the chunk (256-lane multiples) */
         if (n_sets > 1) { --n_sets; return true; }
         if (chunk <= min_chunk) return false;
         chunk = std::max<uint64_t>(min_chunk, ((chunk / 2) + 255) & ~(uint64_t) 255);
         return true;
     };
-    size_t need = 0;
     for (;;) {
-        need = need_of(chunk, n_sets);
+        const size_t need = views_bytes + kStatsBytes + set_bytes_of(pl, chunk) * (size_t) n_sets;
         if (need + other_need > budget) {
             if (shrink()) continue;
             set_error("amvpt_render: the device-memory budget (" + std::to_string(budget >> 20) + " MiB) cannot hold "
@@ -4328,101 +4474,110 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
             A.bytes = 0;
         }
         const amvpt_status as_ = arena_reserve(A, A.base, A.bytes, need, "lane arena");
-        if (as_ == AMVPT_OK) break;
+        if (as_ == AMVPT_OK) return AMVPT_OK;
         if (as_ != AMVPT_ERR_OOM || !shrink()) return as_;
         (void) hipGetLastError();
     }
-    if (P.tile_w && chunk % (4ull * QW * 16ull) != 0) P.tile_w = 0;   /* chunks must hold whole tile bands */
-    P.vs_stride = (uint32_t) chunk;
-    const uint32_t qcap = qcap_of(chunk);
-    const uint64_t qlen = (uint64_t) qcap * kQParts;
+}
+
+/* the side streams and their events: created once per device */
+static amvpt_status side_streams(DevArena &A, int n_sets) {
     for (int k = 0; k + 1 < n_sets; ++k)
         if (!A.side[k]) {
             HIPCHK(hipStreamCreateWithFlags(&A.side[k], hipStreamNonBlocking));
             HIPCHK(hipEventCreateWithFlags(&A.join[k], hipEventDisableTiming));
         }
     if (n_sets > 1 && !A.fork) HIPCHK(hipEventCreateWithFlags(&A.fork, hipEventDisableTiming));
-    arena_release.n_side = n_sets - 1;
-    /* the side stream starts after `st`'s work so far (views upload, counters) */
-    auto fork_side = [&]() -> amvpt_status {
-        if (n_sets < 2 || arena_release.side) return AMVPT_OK;
-        HIPCHK(hipEventRecord(A.fork, st));
-        for (int k = 0; k + 1 < n_sets; ++k) HIPCHK(hipStreamWaitEvent(A.side[k], A.fork, 0));
-        arena_release.side = true;
-        return AMVPT_OK;
-    };
-    char *base = (char *) A.base;
-    DView *dviews = (DView *) base;
-    unsigned long long *dstats = (unsigned long long *) (base + views_bytes);
-    char *p = base + views_bytes + stats_bytes;
-    auto carve = [&](size_t bytes) { char *r = p; p += (bytes + 255) & ~(size_t) 255; return r; };
-    HIPCHK(hipMemcpyAsync(dviews, hv.data(), hv.size() * sizeof(DView), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(dstats, 0, stats_bytes, st));
+    return AMVPT_OK;
+}
 
-    /* deterministic mode: the zeroed 32.32 fixed-point film the splats add into (k_fixed_resolve at the end) */
-    const size_t film_floats = (size_t) QW * QH * (Pp.film_alpha ? 5 : 4);
-    if (private_fx) {
+/* adaptive fill buffers: per-lane mask + compacted lane list for a whole pass */
+struct FillBufs {
+    uint8_t *amask = nullptr;
+    uint32_t *asel = nullptr, *anum = nullptr;
+    uint32_t *runs = nullptr, *delta = nullptr;   /* flagged lanes per run (rect lane sets), run_delta */
+    /* k_select_flagged: one status word per tile + the ticket */
+    unsigned long long *sel_status = nullptr;
+    uint32_t *sel_ticket = nullptr, sel_tiles = 0;
+    size_t sel_bytes = 0;
+};
+
+/* The span-sized buffers: deterministic mode's zeroed 32.32 fixed-point film the splats add into (k_fixed_resolve at
+ * the end), the multi-pass stock path's per-lane sampler states between passes (two planes used in turn), and the
+ * adaptive fill's.  Sets the pointers of P that name them. */
+static amvpt_status reserve_span_buffers(const RenderCall &c, const RenderPlan &pl, DevArena &A, unsigned long long *dstats,
+                                         KParams &P, unsigned long long *carry[2], FillBufs &f) {
+    hipStream_t st = c.st;
+    const size_t film_floats = pl.film_floats;
+    if (pl.private_fx) {
         { const amvpt_status as_ = arena_reserve(A, A.fx, A.fxbytes, film_floats * 8, "deterministic film"); if (as_ != AMVPT_OK) return as_; }
         HIPCHK(hipMemsetAsync(A.fx, 0, film_floats * 8, st));
         P.film_fx = (unsigned long long *) A.fx;
-    } else if (fixed_film) {
-        P.film_fx = reinterpret_cast<unsigned long long *>(film);   /* accumulated into: no clear, no resolve */
+    } else if (c.fixed_film) {
+        P.film_fx = reinterpret_cast<unsigned long long *>(c.fwin.film);   /* accumulated into: no clear, no resolve */
     }
-    if (deterministic) {
-        P.film_base = film;
+    if (pl.deterministic) {
+        P.film_base = c.fwin.film;
         P.fx_drops = dstats + 9 * kStatShards;
-        P.fx_direct = (opts.flags & AMVPT_OPT_FIXED_DIRECT) ? 1u : 0u;
     }
-
-    /* multi-pass stock path: the per-lane sampler states between passes, two planes used in turn */
-    unsigned long long *carry[2] = {nullptr, nullptr};
-    if (rng_carry) {
+    const uint64_t span = pl.span;
+    carry[0] = carry[1] = nullptr;
+    if (pl.rng_carry) {
         { const amvpt_status as_ = arena_reserve(A, A.carry, A.cbytes, (size_t) 16 * span, "sampler states"); if (as_ != AMVPT_OK) return as_; }
         carry[0] = (unsigned long long *) A.carry;
         carry[1] = carry[0] + span;
     }
-
-    /* adaptive fill buffers: per-lane mask + compacted lane list for a whole pass */
-    uint8_t *d_amask = nullptr;
-    uint32_t *d_asel = nullptr, *d_anum = nullptr, *d_runs = nullptr, *d_delta = nullptr;
-    unsigned long long *d_sel_status = nullptr;
-    uint32_t *d_sel_ticket = nullptr;
-    const uint64_t span_all = span;
-    const size_t runs_bytes = 4 * (((size_t) n_runs + 63) & ~(size_t) 63);
-    /* k_select_flagged: one status word per tile + the ticket */
-    const uint32_t sel_tiles = (uint32_t) ((span_all + kSelTile - 1) / kSelTile);
-    const size_t sel_bytes = 8 * (((size_t) sel_tiles + 31) & ~(size_t) 31) + 256;
-    if (do_fill && span_all > 0xffffffffull) {
+    const size_t runs_bytes = 4 * (((size_t) pl.n_runs + 63) & ~(size_t) 63);
+    f.sel_tiles = (uint32_t) ((span + kSelTile - 1) / kSelTile);
+    f.sel_bytes = 8 * (((size_t) f.sel_tiles + 31) & ~(size_t) 31) + 256;
+    if (pl.do_fill && span > 0xffffffffull) {
         set_error("amvpt_render: adaptive fill over a lane set of 2^32 or more lanes (32-bit lane indices)");
         return AMVPT_ERR_UNSUPPORTED;
     }
-    if (do_fill) {
-        const size_t abytes = ((span_all + 255) & ~(uint64_t) 255) + 4 * ((span_all + 63) & ~(uint64_t) 63) + 256 +
-                              2 * runs_bytes + sel_bytes;
+    if (pl.do_fill) {
+        const size_t abytes = ((span + 255) & ~(uint64_t) 255) + 4 * ((span + 63) & ~(uint64_t) 63) + 256 +
+                              2 * runs_bytes + f.sel_bytes;
         { const amvpt_status as_ = arena_reserve(A, A.adapt, A.abytes, abytes, "adaptive buffers"); if (as_ != AMVPT_OK) return as_; }
         char *ap = (char *) A.adapt;
-        d_amask = (uint8_t *) ap; ap += (span_all + 255) & ~(uint64_t) 255;
-        d_asel = (uint32_t *) ap; ap += 4 * ((span_all + 63) & ~(uint64_t) 63);
-        d_anum = (uint32_t *) ap; ap += 256;
-        d_runs = (uint32_t *) ap; ap += runs_bytes;     /* flagged lanes per run (rect lane sets) */
-        d_delta = (uint32_t *) ap; ap += runs_bytes;    /* run_delta */
-        d_sel_status = (unsigned long long *) ap;
-        d_sel_ticket = (uint32_t *) (ap + sel_bytes - 256);
+        f.amask = (uint8_t *) ap; ap += (span + 255) & ~(uint64_t) 255;
+        f.asel = (uint32_t *) ap; ap += 4 * ((span + 63) & ~(uint64_t) 63);
+        f.anum = (uint32_t *) ap; ap += 256;
+        f.runs = (uint32_t *) ap; ap += runs_bytes;
+        f.delta = (uint32_t *) ap; ap += runs_bytes;
+        f.sel_status = (unsigned long long *) ap;
+        f.sel_ticket = (uint32_t *) (ap + f.sel_bytes - 256);
     }
+    return AMVPT_OK;
+}
 
-    /* one buffer set per chunk stream: queues A / B and their counters, the chunk's lane arena */
-    struct ChunkSet {
-        Bufs B{};
-        float4 *qa[kQPlanes], *qb[kQPlanes];
-        uint16_t *ka, *kb;              /* ray binning: bin keys of queues A / B (null: off) */
-        uint32_t *cntA, *cntB, *cntN;   /* [kQParts * kCntStride] each */
-        hipStream_t st;
-    } sets[kMaxChunkStreams];
+/* one buffer set per chunk stream: queues A / B and their counters, the chunk's lane arena */
+struct ChunkSet {
+    Bufs B{};
+    float4 *qa[kQPlanes], *qb[kQPlanes];
+    uint16_t *ka, *kb;              /* ray binning: bin keys of queues A / B (null: off) */
+    uint32_t *cntA, *cntB, *cntN;   /* [kQParts * kCntStride] each */
+    hipStream_t st;
+    /* a chunk's start: the raygen / primary kernels push into queue A (counter A zeroed), B is the other side */
+    amvpt_status reset() {
+        HIPCHK(hipMemsetAsync(cntA, 0, (size_t) kQParts * kCntStride * 4, st));
+        for (int k = 0; k < kQPlanes; ++k) { B.q_out[k] = qa[k]; B.q_in[k] = qb[k]; }
+        B.cnt_out = cntA; B.cnt_in = cntB;
+        B.key_out = ka; B.key_in = kb;
+        return AMVPT_OK;
+    }
+};
+
+/* carve the buffer sets from the arena, from p on */
+static void carve_sets(const RenderCall &c, const RenderPlan &pl, const DevArena &A, char *p, uint64_t chunk,
+                       unsigned long long *dstats, const FillBufs &f, ChunkSet *sets, int n_sets) {
+    auto carve = [&](size_t bytes) { char *r = p; p += (bytes + 255) & ~(size_t) 255; return r; };
+    const uint32_t G = pl.G, qcap = qcap_of(chunk);
+    const uint64_t qlen = (uint64_t) qcap * kQParts;
     for (int si = 0; si < n_sets; ++si) {
         ChunkSet &cs = sets[si];
         Bufs &B = cs.B;
-        cs.st = si == 0 ? st : A.side[si - 1];
-        uint32_t *dcnt = (uint32_t *) carve(cnt_bytes);
+        cs.st = si == 0 ? c.st : A.side[si - 1];
+        uint32_t *dcnt = (uint32_t *) carve(kCntBytes);
         cs.cntA = dcnt; cs.cntB = dcnt + kQParts * kCntStride; cs.cntN = dcnt + 2 * kQParts * kCntStride;
         for (int k = 0; k < kQPlanes; ++k) cs.qa[k] = (float4 *) carve(16 * qlen);
         for (int k = 0; k < kQPlanes; ++k) cs.qb[k] = (float4 *) carve(16 * qlen);
@@ -4435,318 +4590,406 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
         B.occ = (unsigned long long *) carve((size_t) 8 * G * ((chunk + 63) / 64));
         B.cnt_nee = cs.cntN;
         B.qcap = qcap;
-        B.vrec = (float4 *) carve((size_t) (diff_rec ? 4 : 36) * G * chunk);
+        B.vrec = (float4 *) carve((size_t) (pl.diff_rec ? 4 : 36) * G * chunk);
         cs.ka = cs.kb = nullptr;
         B.key_out = B.key_in = B.key_nee = nullptr;
-        if (bin_ext || bin_nee) { B.sray[0] = (float4 *) carve(32 * qlen); B.sray[1] = nullptr; }
-        B.sgb = bin_nee ? (float2 *) carve(8 * qlen) : nullptr;
-        if (bin_ext) { cs.ka = (uint16_t *) carve(2 * qlen); cs.kb = (uint16_t *) carve(2 * qlen); }
-        if (bin_nee) B.key_nee = (uint16_t *) carve(2 * qlen);
-        if (wide) {
-            for (int k = 0; k < mplanes; ++k) B.vreq_w[k] = (uint4 *) carve(16 * chunk);
-            for (int k = 0; k < 3 * mplanes; ++k) B.lmask_w[k] = (uint4 *) carve(16 * chunk);
-            if (vs_global) B.vstate = (float *) carve((size_t) VS_FIELDS * 4 * G * chunk);
+        if (pl.bin_ext || pl.bin_nee) { B.sray[0] = (float4 *) carve(32 * qlen); B.sray[1] = nullptr; }
+        B.sgb = pl.bin_nee ? (float2 *) carve(8 * qlen) : nullptr;
+        if (pl.bin_ext) { cs.ka = (uint16_t *) carve(2 * qlen); cs.kb = (uint16_t *) carve(2 * qlen); }
+        if (pl.bin_nee) B.key_nee = (uint16_t *) carve(2 * qlen);
+        if (pl.wide) {
+            for (int k = 0; k < pl.mplanes; ++k) B.vreq_w[k] = (uint4 *) carve(16 * chunk);
+            for (int k = 0; k < 3 * pl.mplanes; ++k) B.lmask_w[k] = (uint4 *) carve(16 * chunk);
+            if (pl.vs_global) B.vstate = (float *) carve((size_t) VS_FIELDS * 4 * G * chunk);
         }
-        B.film = film;
-        B.records = records;
+        B.film = c.fwin.film;
+        B.records = c.records;
         B.stats = dstats;
-        B.amask = d_amask;
-        B.asel = d_asel;
-        B.run_delta = d_delta;
+        B.amask = f.amask;
+        B.asel = f.asel;
+        B.run_delta = f.delta;
     }
+}
 
-    const DScene *dS = (const DScene *) scene->dev_scene_struct;
-    const uint32_t fused_blocks = AMVPT_FUSED_BLOCKS;
-    const size_t lds = tab_b ? scene->dev.tab_bytes : 0u;                                           /* k_bounce */
-    /* k_suffix_fused: the box triangles staged for box_walk */
-    const size_t box_lds = P.box_screen ? (size_t) scene->n_boxes * 12u * sizeof(DPrim) : 0u;
-    const size_t lds_ext = scene_lds_bytes(scene->dev, trav);                                       /* BVH walks: k_extend, k_shadow, k_vis */
-    /* the two-box BVH walks (DScene::nodes2) for the per-lane suffix walks of BVHs read from device memory: a stack
-     * of kStack2 u32 entries per thread after the kernels' other LDS (AMVPT_OPT_THREADED_BVH keeps the threaded walks) */
-    P.bvh2 = (scene->n_nodes2 && lane_walk && !(opts.flags & AMVPT_OPT_THREADED_BVH)) ? 1u : 0u;
-    const size_t stk_bytes = P.bvh2 ? (size_t) kStack2 * kStk2Stride * 4u : 0u;
-    P.stk_off_ext = (uint32_t) ((lds_ext + 15u) & ~(size_t) 15u);
-    P.stk_off_any = (uint32_t) ((lds_ext + 15u) & ~(size_t) 15u);
-    const size_t lds_close = P.bvh2 ? P.stk_off_ext + stk_bytes : lds_ext;
-    const size_t lds_any = P.bvh2 ? P.stk_off_any + stk_bytes : lds_ext;
-    const size_t lds_prim = tab_p ? scene->dev.tab_bytes + views_lds_bytes(Pp.n_views) : 0u;        /* primary shading */
+/* what the steps of a render that holds its arena share */
+struct RenderCtx {
+    const RenderCall &call; const RenderPlan &pl; KTimer &T; ArenaRelease &release;
+    const DScene *dS; const DView *dviews;
+    ChunkSet *sets; int n_sets; uint64_t chunk;
+    FillBufs fill;
+};
+
+/* the shared suffix (sample_suffix / sample_single loop) over the queue the raygen
+ * or primary kernel filled: one k_bounce launch per depth, ping-pong A <-> B */
+static amvpt_status run_suffix(const RenderCtx &x, const KParams &P, ChunkSet &cs, uint32_t cn) {
+    const RenderPlan &pl = x.pl;
+    const DScene *dS = x.dS;
+    KTimer &T = x.T;
+    Bufs &B = cs.B;
+    hipStream_t st = cs.st;
+    float4 *const *qa = cs.qa, *const *qb = cs.qb;
+    uint32_t *const cntA = cs.cntA, *const cntB = cs.cntB;
+    if (pl.fuse_suffix) {
+        /* one k_suffix_fused launch over the primary queue (A); B's counters are its work counters */
+        for (int k = 0; k < kQPlanes; ++k) { B.q_in[k] = qa[k]; B.q_out[k] = qb[k]; }
+        B.cnt_in = cntA;
+        B.cnt_out = cntB;
+        HIPCHK(hipMemsetAsync(cntB, 0, (size_t) kQParts * kCntStride * 4, st));
+        T.begin(AMVPT_K_SUFFIX, st);
+        hipLaunchKernelGGL(pl.suffix_fused, dim3(kQParts * AMVPT_FUSED_BLOCKS), dim3(256), kFusedParkBytes + pl.lds_bounce + pl.box_lds, st, P, dS, B);
+        T.end(st);
+        HIPCHK(hipGetLastError());
+        HIPCHK(T.err);
+        return AMVPT_OK;
+    }
+    /* a multiple of kQParts blocks: 1..16 per partition */
+    const uint32_t bgrid = kQParts * std::max<uint32_t>(1, std::min<uint32_t>(16, (cn + 256 * kQParts - 1) / (256 * kQParts)));
+    bool a_is_in = true;
+    for (uint32_t bnc = 0; bnc < pl.max_bounces; ++bnc) {
+        for (int k = 0; k < kQPlanes; ++k) {
+            B.q_in[k] = a_is_in ? qa[k] : qb[k];
+            B.q_out[k] = a_is_in ? qb[k] : qa[k];
+        }
+        B.cnt_in = a_is_in ? cntA : cntB;
+        B.cnt_out = a_is_in ? cntB : cntA;
+        B.key_in = a_is_in ? cs.ka : cs.kb;
+        B.key_out = a_is_in ? cs.kb : cs.ka;
+        /* k_extend zeroes cnt_out and cnt_nee */
+        if (pl.bin_ext) {
+            T.begin(AMVPT_K_BIN, st);
+            hipLaunchKernelGGL(bnc == 0 ? pl.bin_rays : pl.bin_paths, dim3(kQParts), dim3(kBinBlock), 0, st, P, B);
+            T.end(st);
+        }
+        T.begin(AMVPT_K_EXTEND, st);
+        hipLaunchKernelGGL(pl.extend, dim3(bgrid), dim3(256), pl.lds_walk2, st, P, dS, B);
+        T.end(st);
+        T.begin(AMVPT_K_BOUNCE, st);
+        hipLaunchKernelGGL(pl.bounce, dim3(bgrid), dim3(256), pl.lds_bounce, st, P, dS, B);
+        T.end(st);
+        if (!pl.fuse_nee) {
+            if (pl.bin_nee) {
+                T.begin(AMVPT_K_BIN, st);
+                hipLaunchKernelGGL(pl.bin_nee_rays, dim3(kQParts), dim3(kBinBlock), 0, st, P, B);
+                T.end(st);
+            }
+            T.begin(AMVPT_K_SHADOW, st);
+            const amvpt_status s = launch_shadow(pl.walk, pl.bin_nee, dim3(bgrid), pl.lds_walk2, st, P, dS, B);
+            T.end(st);
+            if (s != AMVPT_OK) return s;
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(T.err);
+        a_is_in = !a_is_in;
+        if (bnc >= 15 && (bnc & 7) == 7) { /* unbounded depth: poll the live count */
+            std::vector<uint32_t> hc((size_t) kQParts * kCntStride);
+            HIPCHK(hipMemcpyAsync(hc.data(), B.cnt_out, hc.size() * 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            uint64_t live = 0;
+            for (uint32_t q = 0; q < kQParts; ++q) live += hc[(size_t) q * kCntStride];
+            if (live == 0) break;
+        }
+    }
+    return AMVPT_OK;
+}
+
+/* one chunk of a pass: primary vertex, suffix, splat.  Chunk i runs on set i mod n_sets; the side streams start
+ * once the first chunk's primary stage is queued (the streams then run offset from each other) */
+static amvpt_status run_chunk(const RenderCtx &x, KParams P, uint64_t c0, uint64_t chunk_index) {
+    const RenderPlan &pl = x.pl;
+    KTimer &T = x.T;
+    const uint32_t G = pl.G;
+    float *const records = x.call.records;
+    const uint32_t cn = (uint32_t) std::min<uint64_t>(x.chunk, pl.span - c0);
+    ChunkSet &cs = x.sets[chunk_index % (uint64_t) x.n_sets];
+    Bufs &B = cs.B;
+    hipStream_t st = cs.st;
+    amvpt_status s = AMVPT_OK;
+    /* a side chunk never runs before the fork (e.g. after a pass's join) */
+    if (&cs != &x.sets[0] && (s = x.release.fork()) != AMVPT_OK) return s;
+    P.chunk_begin = c0;
+    P.chunk_n = cn;
+    B.records = P.record ? records + (size_t) c0 * G * 8 : records;
+    const dim3 grid((cn + 255) / 256);
+    if ((s = cs.reset()) != AMVPT_OK) return s;
+    T.mark(st);
+    {
+        RoctxScope range_primary("amvpt primary vertex (raygen, visibility, camera selection, MIS)");
+        if (G == 1) {
+            T.begin(AMVPT_K_RAYGEN, st);
+            hipLaunchKernelGGL(k_raygen_single, grid, dim3(256), 0, st, P, x.dviews, B);
+            T.end(st);
+        } else {
+            s = kPrimary[dispatch_g(G)](cn, pl.lds_prim, pl.lds_ext, st, P, x.dS, x.dviews, B, pl.tab_p, pl.uni_coh, pl.diff_rec, T);
+        }
+    }
+    if (s != AMVPT_OK) return s;
+    HIPCHK(hipGetLastError());
+    HIPCHK(T.err);
+    T.mark(st);
+    /* the side streams' start: after this primary stage */
+    if (x.n_sets > 1 && chunk_index % (uint64_t) x.n_sets == 0 && (s = x.release.fork()) != AMVPT_OK) return s;
+    {
+        RoctxScope range_suffix("amvpt shared suffix (extend, bounce, NEE)");
+        if ((s = run_suffix(x, P, cs, cn)) != AMVPT_OK) return s;
+    }
+    T.mark(st);
+    RoctxScope range_splat("amvpt splat (ImageBlock::put)");
+    const dim3 sgrid((cn + kSplatBlock - 1) / kSplatBlock);
+    T.begin(AMVPT_K_SPLAT, st);
+    if (G == 1) hipLaunchKernelGGL(pl.splat.single, sgrid, dim3(kSplatBlock), 0, st, P, B);
+    else s = kSplat[dispatch_g(G)](sgrid, st, P, x.dviews, B, pl.diff_rec);
+    T.end(st);
+    T.mark(st);
+    if (s != AMVPT_OK) return s;
+    HIPCHK(hipGetLastError());
+    if (x.n_sets < 2) T.flush();
+    HIPCHK(T.err);
+    return AMVPT_OK;
+}
+
+/* The fill's host arithmetic: this render's place in the pass's compressed array as run_delta = global - local
+ * prefix per run, from the prefixes the exchange returned (empty: the whole frame, nothing to place) */
+static amvpt_status fill_run_delta(const std::vector<uint64_t> &run_prefix, const std::vector<uint64_t> &run_count,
+                                   uint64_t n_sel, uint64_t total, uint32_t n_adapt, std::vector<uint32_t> &delta) {
+    uint64_t local = 0;
+    for (size_t r = 0; r < run_prefix.size(); ++r) {
+        if (run_prefix[r] < local || run_prefix[r] + run_count[r] > total) {
+            set_error("amvpt_render: adaptive count exchange returned inconsistent prefixes");
+            return AMVPT_ERR_INVALID;
+        }
+        delta[r] = (uint32_t) (run_prefix[r] - local);
+        local += run_count[r];
+    }
+    if (!run_prefix.empty() && local != n_sel) {
+        set_error("amvpt_render: per-run adaptive counts disagree with the compaction");
+        return AMVPT_ERR_INVALID;
+    }
+    if (total * n_adapt > 0xffffffffull) { set_error("amvpt_render: adaptive wavefront over 2^32 lanes"); return AMVPT_ERR_UNSUPPORTED; }
+    return AMVPT_OK;
+}
+
+/* compact the pass's adapt_mask lanes in lane order (virtual indices of the lane set, ascending = lane order) and
+ * place them in the whole pass's array (one exchange per pass): n_sel, the pass's total, run_delta on the device */
+static amvpt_status fill_select(const RenderCtx &x, const KParams &P, uint64_t &n_sel, uint64_t &total) {
+    const RenderPlan &pl = x.pl;
+    const FillBufs &f = x.fill;
+    KTimer &T = x.T;
+    hipStream_t st = x.call.st;
+    const uint32_t n_runs = pl.n_runs;
+    HIPCHK(hipMemsetAsync(f.sel_status, 0, f.sel_bytes, st));   /* status words + ticket */
+    T.begin(AMVPT_K_SELECT, st);
+    hipLaunchKernelGGL(k_select_flagged, dim3(f.sel_tiles), dim3(256), 0, st, (const uint8_t *) f.amask, pl.span,
+                       f.asel, f.anum, f.sel_status, f.sel_ticket, f.sel_tiles);
+    T.end(st);
+    HIPCHK(hipGetLastError());
+    uint32_t got = 0;
+    HIPCHK(hipMemcpyAsync(&got, f.anum, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    n_sel = total = got;
+    std::vector<uint32_t> delta(n_runs, 0u);
+    std::vector<uint64_t> run_begin, run_count, run_prefix;
+    if (pl.partial) {
+        run_begin.resize(n_runs); run_count.assign(n_runs, 0); run_prefix.assign(n_runs, 0);
+        if (pl.rect) {
+            hipLaunchKernelGGL(k_run_counts, dim3(n_runs), dim3(256), 0, st, (const uint8_t *) f.amask, P.run_len, f.runs);
+            HIPCHK(hipGetLastError());
+            std::vector<uint32_t> rc(n_runs);
+            HIPCHK(hipMemcpyAsync(rc.data(), f.runs, 4 * (size_t) n_runs, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            for (uint32_t r = 0; r < n_runs; ++r) {
+                run_count[r] = rc[r];
+                run_begin[r] = ((uint64_t) (pl.ry0 + r) * P.W + pl.rx0) * pl.spp_pp;
+            }
+        } else {
+            run_count[0] = n_sel;
+            run_begin[0] = pl.lane_begin;
+        }
+        if (x.call.opts.exchange(x.call.opts.exchange_ctx, n_runs, run_begin.data(), run_count.data(), run_prefix.data(), &total) != 0) {
+            set_error("amvpt_render: adaptive count exchange failed");
+            return AMVPT_ERR_INVALID;
+        }
+    }
+    const amvpt_status s = fill_run_delta(run_prefix, run_count, n_sel, total, pl.n_adapt, delta);
+    if (s != AMVPT_OK) return s;
+    HIPCHK(hipMemcpyAsync(f.delta, delta.data(), 4 * (size_t) n_runs, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));   /* `delta` is a host temporary */
+    return AMVPT_OK;
+}
+
+/* the adaptive fill of a pass (P: the pass's parameters): the compacted lanes re-traced n_adapt times each, in
+ * chunks on the render stream's buffer set */
+static amvpt_status run_fill(const RenderCtx &x, KParams P, uint64_t &adaptive_lanes) {
+    const RenderPlan &pl = x.pl;
+    KTimer &T = x.T;
+    hipStream_t st = x.call.st;
+    RoctxScope range_fill("amvpt adaptive fill");
+    uint64_t n_sel = 0, total = 0;
+    amvpt_status s = fill_select(x, P, n_sel, total);
+    if (s != AMVPT_OK) return s;
+    const uint64_t wf = n_sel * pl.n_adapt;
+    adaptive_lanes += wf;
+    P.pass_seed = P.seed_value;
+    P.adapt_seed = x.call.Pp.base_seed + (uint32_t) (total * pl.n_adapt);   /* sampler->fork(); seed(wavefront, wavefront) */
+    P.adapt_pass = 1;
+    P.record = 0;
+    ChunkSet &cs = x.sets[0];
+    Bufs &B = cs.B;
+    for (uint64_t c0 = 0; c0 < wf; c0 += x.chunk) {
+        const uint32_t cn = (uint32_t) std::min<uint64_t>(x.chunk, wf - c0);
+        P.chunk_begin = c0;
+        P.chunk_n = cn;
+        if ((s = cs.reset()) != AMVPT_OK) return s;
+        T.begin(AMVPT_K_RAYGEN, st);
+        hipLaunchKernelGGL(k_raygen_adapt, dim3((cn + 255) / 256), dim3(256), 0, st, P, x.dviews, B);
+        T.end(st);
+        HIPCHK(hipGetLastError());
+        if ((s = run_suffix(x, P, cs, cn)) != AMVPT_OK) return s;
+        const dim3 sgrid((cn + kSplatBlock - 1) / kSplatBlock);
+        T.begin(AMVPT_K_SPLAT, st);
+        hipLaunchKernelGGL(pl.splat.adapt, sgrid, dim3(kSplatBlock), 0, st, P, B);
+        T.end(st);
+        HIPCHK(hipGetLastError());
+        T.flush();
+        HIPCHK(T.err);
+    }
+    return AMVPT_OK;
+}
+
+static amvpt_status read_counters(const RenderCtx &x, const DevArena &A, const unsigned long long *dstats,
+                                  uint64_t adaptive_lanes, uint64_t overflow_added,
+                                  std::chrono::steady_clock::time_point t0) {
+    const RenderPlan &pl = x.pl;
+    KTimer &T = x.T;
+    hipStream_t st = x.call.st;
+    std::vector<unsigned long long> hsh((size_t) kStats * kStatShards);
+    HIPCHK(hipMemcpyAsync(hsh.data(), dstats, kStatsBytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    unsigned long long hs[kStats] = {0};
+    for (uint32_t k = 0; k < kStats; ++k)
+        for (uint32_t q = 0; q < kStatShards; ++q) hs[k] += hsh[(size_t) k * kStatShards + q];
+    amvpt_counters &c = *x.call.counters;
+    c = amvpt_counters{};
+    c.lanes = pl.span * pl.n_passes;
+    c.passes = pl.n_passes;
+    c.vertices = hs[0];
+    c.reuse_lanes = hs[1];
+    c.visibility_rays = hs[2];
+    c.view_splats = hs[3];
+    c.splat_fallback = hs[4];
+    c.adaptive_lanes = adaptive_lanes;
+    c.shadow_rays = hs[5];
+    c.record_bytes = pl.G > 1 ? 64 + 16 + (pl.diff_rec ? 4 : 32) * (uint64_t) pl.G : 0;
+    c.nonfinite_samples = hs[6];
+    c.negative_samples = hs[7];
+    c.pushed_paths = hs[8];
+    c.film_overflow = overflow_added;   /* this render's cells (renders append to the list) */
+    c.film_range_drops = hs[9];
+    c.primary_record_bytes = hs[10];
+    c.splat_record_bytes = hs[11];
+    c.chunk_lanes = x.chunk;
+    c.buffer_sets = (uint64_t) x.n_sets;
+    c.arena_bytes = A.bytes + A.abytes + A.fxbytes + A.cbytes;
+    T.flush();
+    HIPCHK(T.err);
+    for (int k = 0; k < AMVPT_K_COUNT; ++k) { c.kernel_ms[k] = T.ms[k]; c.kernel_launches[k] = T.launches[k]; }
+    c.kernel_ms_primary = T.ms[AMVPT_K_PRIM_HIT] + T.ms[AMVPT_K_PRIM_REQ] + T.ms[AMVPT_K_VIS] +
+                          T.ms[AMVPT_K_MV_PRIMARY] + T.ms[AMVPT_K_RAYGEN];
+    c.kernel_ms_bounce = T.ms[AMVPT_K_EXTEND] + T.ms[AMVPT_K_BOUNCE] + T.ms[AMVPT_K_SHADOW] + T.ms[AMVPT_K_SUFFIX];
+    c.kernel_ms_splat = T.ms[AMVPT_K_SPLAT];
+    c.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return AMVPT_OK;
+}
+
+/*
+ * One render: plan -> arena (chunk size, buffer sets) -> per pass { per chunk { primary vertex -> suffix -> splat }
+ * -> adaptive fill } -> fixed-point resolve -> overflow check -> counters.
+ */
+amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const amvpt_params *params,
+                         const amvpt_lane_set &lanes, const amvpt_film_window &fwin, void *stream,
+                         const amvpt_render_opts &opts, amvpt_counters *counters, float *records,
+                         uint32_t record_pass, bool fixed_film) {
+    float *const film = fwin.film;
+    if (!scene || !views || !params || !film) { set_error("amvpt_render: null argument"); return AMVPT_ERR_INVALID; }
+    RoctxScope range_render("amvpt_render");
+    hipStream_t st = (hipStream_t) stream;
+    const RenderCall call{scene, views, *params, lanes, fwin, st, opts, counters, records, record_pass, fixed_film};
+    RenderPlan plan_;
+    amvpt_status s = make_plan(call, plan_);
+    if (s != AMVPT_OK) return s;
+    const RenderPlan &pl = plan_;
+    if (pl.span == 0) return render_nothing(call, pl);
+
+    KParams P = pl.P;
+    /* the list's count before this render: renders append (amvpt_film_window), film_overflow reports the
+     * cells this one added */
+    uint64_t overflow_before = 0, overflow_added = 0;
+    if (P.overflow) {
+        HIPCHK(hipMemcpyAsync(&overflow_before, P.overflow, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    const std::vector<DView> hv = host_views(call);
+    const size_t views_bytes = ((hv.size() * sizeof(DView)) + 255) & ~(size_t) 255;
+
+    int dev = 0;
+    HIPCHK(hipGetDevice(&dev));
+    DevArena &A = dev_arena(dev);
+    std::unique_lock<std::mutex> arena_lock(A.mu);
+    if (!A.done) HIPCHK(hipEventCreateWithFlags(&A.done, hipEventDisableTiming));
+    /* the previous render's buffers may still be in flight on another stream */
+    if (A.pending && A.last != st) HIPCHK(hipStreamWaitEvent(st, A.done, 0));
+    ArenaRelease arena_release{A, st, 0};
+    uint64_t chunk = 0;
+    int n_sets = 0;
+    if ((s = size_arena(call, pl, A, views_bytes, chunk, n_sets)) != AMVPT_OK) return s;
+    if (P.tile_w && chunk % (4ull * P.W * 16ull) != 0) P.tile_w = 0;   /* chunks must hold whole tile bands */
+    P.vs_stride = (uint32_t) chunk;
+    if ((s = side_streams(A, n_sets)) != AMVPT_OK) return s;
+    arena_release.n_side = n_sets - 1;
+
+    /* the arena: views, counters, then the buffer sets */
+    char *base = (char *) A.base;
+    DView *dviews = (DView *) base;
+    unsigned long long *dstats = (unsigned long long *) (base + views_bytes);
+    HIPCHK(hipMemcpyAsync(dviews, hv.data(), hv.size() * sizeof(DView), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(dstats, 0, kStatsBytes, st));
+    unsigned long long *carry[2];
+    FillBufs fill;
+    if ((s = reserve_span_buffers(call, pl, A, dstats, P, carry, fill)) != AMVPT_OK) return s;
+    ChunkSet sets[kMaxChunkStreams];
+    carve_sets(call, pl, A, base + views_bytes + kStatsBytes, chunk, dstats, fill, sets, n_sets);
+
     KTimer T;
     T.init(counters != nullptr);
     HIPCHK(T.err);
     auto t0 = std::chrono::steady_clock::now();
-    const uint32_t max_bounces = P.max_depth == 0xffffffffu ? 0xffffffffu : P.max_depth + 1;
-
-    /* the shared suffix (sample_suffix / sample_single loop) over the queue the raygen
-     * or primary kernel filled: one k_bounce launch per depth, ping-pong A <-> B */
-    auto run_suffix = [&](ChunkSet &cs, uint32_t cn) -> amvpt_status {
-        Bufs &B = cs.B;
-        hipStream_t st = cs.st;
-        float4 *const *qa = cs.qa, *const *qb = cs.qb;
-        uint32_t *const cntA = cs.cntA, *const cntB = cs.cntB;
-        if (fuse_suffix) {
-            /* one k_suffix_fused launch over the primary queue (A); B's counters are its work counters */
-            for (int k = 0; k < kQPlanes; ++k) { B.q_in[k] = qa[k]; B.q_out[k] = qb[k]; }
-            B.cnt_in = cntA;
-            B.cnt_out = cntB;
-            HIPCHK(hipMemsetAsync(cntB, 0, (size_t) kQParts * kCntStride * 4, st));
-            T.begin(AMVPT_K_SUFFIX, st);
-            launch_suffix_fused(tab_b, diff, walk, dim3(kQParts * fused_blocks), kFusedParkBytes + lds + box_lds, st, P, dS, B);
-            T.end(st);
-            HIPCHK(hipGetLastError());
-            HIPCHK(T.err);
-            return AMVPT_OK;
-        }
-        /* a multiple of kQParts blocks: 1..16 per partition */
-        const uint32_t bgrid = kQParts * std::max<uint32_t>(1, std::min<uint32_t>(16, (cn + 256 * kQParts - 1) / (256 * kQParts)));
-        bool a_is_in = true;
-        for (uint32_t bnc = 0; bnc < max_bounces; ++bnc) {
-            for (int k = 0; k < kQPlanes; ++k) {
-                B.q_in[k] = a_is_in ? qa[k] : qb[k];
-                B.q_out[k] = a_is_in ? qb[k] : qa[k];
-            }
-            B.cnt_in = a_is_in ? cntA : cntB;
-            B.cnt_out = a_is_in ? cntB : cntA;
-            B.key_in = a_is_in ? cs.ka : cs.kb;
-            B.key_out = a_is_in ? cs.kb : cs.ka;
-            /* k_extend zeroes cnt_out and cnt_nee */
-            if (bin_ext) {
-                T.begin(AMVPT_K_BIN, st);
-                if (bnc == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bin_sort<false, true>), dim3(kQParts), dim3(kBinBlock), 0, st, P, B);
-                else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bin_sort<false>), dim3(kQParts), dim3(kBinBlock), 0, st, P, B);
-                T.end(st);
-            }
-            T.begin(AMVPT_K_EXTEND, st);
-            if (bin_ext && walk == WALK_LANE_TRI) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_extend<WALK_LANE_TRI, true>), dim3(bgrid), dim3(256), lds_close, st, P, dS, B);
-            else if (bin_ext && walk == WALK_LANE_NS) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_extend<WALK_LANE_NS, true>), dim3(bgrid), dim3(256), lds_close, st, P, dS, B);
-            else if (bin_ext) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_extend<WALK_LANE, true>), dim3(bgrid), dim3(256), lds_close, st, P, dS, B);
-            else if (walk == WALK_BRUTE_NS) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_extend<WALK_BRUTE_NS>), dim3(bgrid), dim3(256), lds_ext, st, P, dS, B);
-            else if (walk == WALK_BRUTE) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_extend<WALK_BRUTE>), dim3(bgrid), dim3(256), lds_ext, st, P, dS, B);
-            else if (walk == WALK_UNI) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_extend<WALK_UNI>), dim3(bgrid), dim3(256), lds_ext, st, P, dS, B);
-            else if (walk == WALK_LANE_TRI) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_extend<WALK_LANE_TRI>), dim3(bgrid), dim3(256), lds_close, st, P, dS, B);
-            else if (walk == WALK_LANE_NS) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_extend<WALK_LANE_NS>), dim3(bgrid), dim3(256), lds_close, st, P, dS, B);
-            else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_extend<WALK_LANE>), dim3(bgrid), dim3(256), lds_close, st, P, dS, B);
-            T.end(st);
-            T.begin(AMVPT_K_BOUNCE, st);
-            launch_bounce(tab_b, diff, fuse_nee ? walk : -1, dim3(bgrid), lds, st, P, dS, B);
-            T.end(st);
-            if (!fuse_nee) {
-                if (bin_nee) {
-                    T.begin(AMVPT_K_BIN, st);
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bin_sort<true>), dim3(kQParts), dim3(kBinBlock), 0, st, P, B);
-                    T.end(st);
-                }
-                T.begin(AMVPT_K_SHADOW, st);
-                launch_shadow(walk, bin_nee, dim3(bgrid), lds_any, st, P, dS, B);
-                T.end(st);
-            }
-            HIPCHK(hipGetLastError());
-            HIPCHK(T.err);
-            a_is_in = !a_is_in;
-            if (bnc >= 15 && (bnc & 7) == 7) { /* unbounded depth: poll the live count */
-                std::vector<uint32_t> hc((size_t) kQParts * kCntStride);
-                HIPCHK(hipMemcpyAsync(hc.data(), B.cnt_out, hc.size() * 4, hipMemcpyDeviceToHost, st));
-                HIPCHK(hipStreamSynchronize(st));
-                uint64_t live = 0;
-                for (uint32_t q = 0; q < kQParts; ++q) live += hc[(size_t) q * kCntStride];
-                if (live == 0) break;
-            }
-        }
-        return AMVPT_OK;
-    };
-    uint64_t adaptive_lanes = 0;
-
-    uint64_t chunk_index = 0;
-    for (uint32_t pass = 0; pass < n_passes; ++pass) {
+    const RenderCtx ctx{call, pl, T, arena_release, (const DScene *) scene->dev_scene_struct, dviews, sets, n_sets, chunk, fill};
+    uint64_t adaptive_lanes = 0, chunk_index = 0;
+    for (uint32_t pass = 0; pass < pl.n_passes; ++pass) {
         RoctxScope range_pass("amvpt pass");
-        P.seed_value = Pp.base_seed + (is_mv ? (spp_pp * pass + Pp.seed) : Pp.seed);
+        P.seed_value = params->base_seed + (pl.is_mv ? (pl.spp_pp * pass + params->seed) : params->seed);
         P.record = (records && pass == record_pass) ? 1u : 0u;
-        P.rng_in = rng_carry && pass > 0 ? carry[pass & 1u] : nullptr;
-        P.rng_out = rng_carry && pass + 1 < n_passes ? carry[(pass + 1) & 1u] : nullptr;
-        for (uint64_t c0 = 0; c0 < span; c0 += chunk, ++chunk_index) {   /* virtual indices of the lane set */
-            const uint32_t cn = (uint32_t) std::min<uint64_t>(chunk, span - c0);
-            /* chunk i on set i mod n_sets: the side streams start once the first chunk's primary stage is queued
-             * (the streams then run offset from each other) */
-            ChunkSet &cs = sets[chunk_index % (uint64_t) n_sets];
-            Bufs &B = cs.B;
-            hipStream_t st = cs.st;
-            uint32_t *const cntA = cs.cntA, *const cntB = cs.cntB;
-            float4 *const *qa = cs.qa, *const *qb = cs.qb;
-            if (&cs != &sets[0]) {   /* a side chunk never runs before the fork (e.g. after a pass's join) */
-                const amvpt_status fs_ = fork_side();
-                if (fs_ != AMVPT_OK) return fs_;
-            }
-            P.chunk_begin = c0;
-            P.chunk_n = cn;
-            B.records = P.record ? records + (size_t) c0 * G * 8 : records;
-            const dim3 grid((cn + 255) / 256);
-            /* counters: [0] = queue A, [1] = queue B */
-            HIPCHK(hipMemsetAsync(cntA, 0, (size_t) kQParts * kCntStride * 4, st));
-            for (int k = 0; k < kQPlanes; ++k) { B.q_out[k] = qa[k]; B.q_in[k] = qb[k]; }
-            B.cnt_out = cntA; B.cnt_in = cntB;
-            B.key_out = cs.ka; B.key_in = cs.kb;
-            T.mark(st);
-            {
-                RoctxScope range_primary("amvpt primary vertex (raygen, visibility, camera selection, MIS)");
-                if (G == 1) {
-                    T.begin(AMVPT_K_RAYGEN, st);
-                    hipLaunchKernelGGL(k_raygen_single, grid, dim3(256), 0, st, P, dviews, B);
-                    T.end(st);
-                } else {
-                    kPrimary[dispatch_g(G)](cn, lds_prim, lds_ext, st, P, dS, dviews, B, tab_p, uni_coh, diff, T);
-                }
-            }
-            HIPCHK(hipGetLastError());
-            HIPCHK(T.err);
-            T.mark(st);
-            if (n_sets > 1 && chunk_index % (uint64_t) n_sets == 0) {   /* the side streams' start: after this primary stage */
-                const amvpt_status fs_ = fork_side();
-                if (fs_ != AMVPT_OK) return fs_;
-            }
-            /* suffix bounces: ping-pong A <-> B */
-            {
-                RoctxScope range_suffix("amvpt shared suffix (extend, bounce, NEE)");
-                const amvpt_status rs_ = run_suffix(cs, cn);
-                if (rs_ != AMVPT_OK) return rs_;
-            }
-            T.mark(st);
-            RoctxScope range_splat("amvpt splat (ImageBlock::put)");
-            const dim3 sgrid((cn + kSplatBlock - 1) / kSplatBlock);
-            T.begin(AMVPT_K_SPLAT, st);
-            const bool any_filt = P.filt_kind > FILT_GAUSSIAN;   /* FK_ANY instances (tent, Mitchell, Catmull-Rom, Lanczos) */
-            if (G == 1 && P.film_fx) {
-                if (P.C == 5 && any_filt) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_single<5, FK_ANY, true>), sgrid, dim3(kSplatBlock), 0, st, P, B);
-                else if (any_filt) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_single<4, FK_ANY, true>), sgrid, dim3(kSplatBlock), 0, st, P, B);
-                else if (P.C == 5) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_single<5, FK_LEGACY, true>), sgrid, dim3(kSplatBlock), 0, st, P, B);
-                else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_single<4, FK_LEGACY, true>), sgrid, dim3(kSplatBlock), 0, st, P, B);
-            }
-            else if (G == 1 && P.C == 5 && any_filt) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_single<5, FK_ANY>), sgrid, dim3(kSplatBlock), 0, st, P, B);
-            else if (G == 1 && any_filt) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_single<4, FK_ANY>), sgrid, dim3(kSplatBlock), 0, st, P, B);
-            else if (G == 1 && P.C == 5) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_single<5>), sgrid, dim3(kSplatBlock), 0, st, P, B);
-            else if (G == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_single<4>), sgrid, dim3(kSplatBlock), 0, st, P, B);
-            else kSplat[dispatch_g(G)](sgrid, st, P, dviews, B, diff_rec);
-            T.end(st);
-            T.mark(st);
-            HIPCHK(hipGetLastError());
-            if (n_sets < 2) T.flush();
-            HIPCHK(T.err);
-        }
+        P.rng_in = pl.rng_carry && pass > 0 ? carry[pass & 1u] : nullptr;
+        P.rng_out = pl.rng_carry && pass + 1 < pl.n_passes ? carry[(pass + 1) & 1u] : nullptr;
+        for (uint64_t c0 = 0; c0 < pl.span; c0 += chunk, ++chunk_index)   /* virtual indices of the lane set */
+            if ((s = run_chunk(ctx, P, c0, chunk_index)) != AMVPT_OK) return s;
         /* the stock path's next pass reads the sampler states this pass writes (and writes the plane this
          * pass read): with two chunk streams, chunk c of the next pass may run on the other stream than chunk
          * c of this one, so both streams meet at every pass boundary (the next side chunk forks again) */
-        if (rng_carry) arena_release.join();
-        if (do_fill) {
-            /* the fill reads the whole pass's adapt_mask: both chunk streams first */
-            arena_release.join();
-            RoctxScope range_fill("amvpt adaptive fill");
-            /* compact the pass's adapt_mask lanes in lane order (virtual indices of the lane set,
-             * ascending = lane order), then n_adapt re-traces each */
-            uint64_t n_sel = 0;
-            {
-                HIPCHK(hipMemsetAsync(d_sel_status, 0, sel_bytes, st));   /* status words + ticket */
-                T.begin(AMVPT_K_SELECT, st);
-                hipLaunchKernelGGL(k_select_flagged, dim3(sel_tiles), dim3(256), 0, st, (const uint8_t *) d_amask, span_all,
-                                   d_asel, d_anum, d_sel_status, d_sel_ticket, sel_tiles);
-                T.end(st);
-                HIPCHK(hipGetLastError());
-                uint32_t got = 0;
-                HIPCHK(hipMemcpyAsync(&got, d_anum, 4, hipMemcpyDeviceToHost, st));
-                HIPCHK(hipStreamSynchronize(st));
-                n_sel = got;
-            }
-            /* this render's place in the pass's compressed array: per run, the flagged lanes of the
-             * whole pass below it (one exchange per pass), as run_delta = global - local prefix */
-            uint64_t total = n_sel;
-            std::vector<uint32_t> delta(n_runs, 0u);
-            if (partial) {
-                std::vector<uint64_t> run_begin(n_runs), run_count(n_runs, 0), run_prefix(n_runs, 0);
-                if (rect) {
-                    hipLaunchKernelGGL(k_run_counts, dim3(n_runs), dim3(256), 0, st, (const uint8_t *) d_amask, P.run_len, d_runs);
-                    HIPCHK(hipGetLastError());
-                    std::vector<uint32_t> rc(n_runs);
-                    HIPCHK(hipMemcpyAsync(rc.data(), d_runs, 4 * (size_t) n_runs, hipMemcpyDeviceToHost, st));
-                    HIPCHK(hipStreamSynchronize(st));
-                    for (uint32_t r = 0; r < n_runs; ++r) {
-                        run_count[r] = rc[r];
-                        run_begin[r] = ((uint64_t) (ry0 + r) * QW + rx0) * spp_pp;
-                    }
-                } else {
-                    run_count[0] = n_sel;
-                    run_begin[0] = lane_begin;
-                }
-                if (exchange(exchange_ctx, n_runs, run_begin.data(), run_count.data(), run_prefix.data(), &total) != 0) {
-                    set_error("amvpt_render: adaptive count exchange failed");
-                    return AMVPT_ERR_INVALID;
-                }
-                uint64_t local = 0;
-                for (uint32_t r = 0; r < n_runs; ++r) {
-                    if (run_prefix[r] < local || run_prefix[r] + run_count[r] > total) {
-                        set_error("amvpt_render: adaptive count exchange returned inconsistent prefixes");
-                        return AMVPT_ERR_INVALID;
-                    }
-                    delta[r] = (uint32_t) (run_prefix[r] - local);
-                    local += run_count[r];
-                }
-                if (local != n_sel) {
-                    set_error("amvpt_render: per-run adaptive counts disagree with the compaction");
-                    return AMVPT_ERR_INVALID;
-                }
-            }
-            if (total * n_adapt > 0xffffffffull) { set_error("amvpt_render: adaptive wavefront over 2^32 lanes"); return AMVPT_ERR_UNSUPPORTED; }
-            HIPCHK(hipMemcpyAsync(d_delta, delta.data(), 4 * (size_t) n_runs, hipMemcpyHostToDevice, st));
-            HIPCHK(hipStreamSynchronize(st));   /* `delta` is a host temporary */
-            const uint64_t wf = n_sel * n_adapt;
-            adaptive_lanes += wf;
-            KParams Ps = P;
-            P.pass_seed = P.seed_value;
-            P.adapt_seed = Pp.base_seed + (uint32_t) (total * n_adapt);   /* sampler->fork(); seed(wavefront, wavefront) */
-            P.adapt_pass = 1;
-            P.record = 0;
-            ChunkSet &cs = sets[0];
-            Bufs &B = cs.B;
-            uint32_t *const cntA = cs.cntA, *const cntB = cs.cntB;
-            float4 *const *qa = cs.qa, *const *qb = cs.qb;
-            for (uint64_t c0 = 0; c0 < wf; c0 += chunk) {
-                const uint32_t cn = (uint32_t) std::min<uint64_t>(chunk, wf - c0);
-                P.chunk_begin = c0;
-                P.chunk_n = cn;
-                HIPCHK(hipMemsetAsync(cntA, 0, (size_t) kQParts * kCntStride * 4, st));
-                for (int k = 0; k < kQPlanes; ++k) { B.q_out[k] = qa[k]; B.q_in[k] = qb[k]; }
-                B.cnt_out = cntA; B.cnt_in = cntB;
-                B.key_out = cs.ka; B.key_in = cs.kb;
-                T.begin(AMVPT_K_RAYGEN, st);
-                hipLaunchKernelGGL(k_raygen_adapt, dim3((cn + 255) / 256), dim3(256), 0, st, P, dviews, B);
-                T.end(st);
-                HIPCHK(hipGetLastError());
-                { const amvpt_status rs_ = run_suffix(cs, cn); if (rs_ != AMVPT_OK) return rs_; }
-                const dim3 sgrid((cn + kSplatBlock - 1) / kSplatBlock);
-                T.begin(AMVPT_K_SPLAT, st);
-                if (P.film_fx) {
-                    if (P.C == 5 && P.filt_kind > FILT_GAUSSIAN) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_adapt<5, FK_ANY, true>), sgrid, dim3(kSplatBlock), 0, st, P, B);
-                    else if (P.filt_kind > FILT_GAUSSIAN) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_adapt<4, FK_ANY, true>), sgrid, dim3(kSplatBlock), 0, st, P, B);
-                    else if (P.C == 5) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_adapt<5, FK_LEGACY, true>), sgrid, dim3(kSplatBlock), 0, st, P, B);
-                    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_adapt<4, FK_LEGACY, true>), sgrid, dim3(kSplatBlock), 0, st, P, B);
-                }
-                else if (P.C == 5 && P.filt_kind > FILT_GAUSSIAN) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_adapt<5, FK_ANY>), sgrid, dim3(kSplatBlock), 0, st, P, B);
-                else if (P.filt_kind > FILT_GAUSSIAN) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_adapt<4, FK_ANY>), sgrid, dim3(kSplatBlock), 0, st, P, B);
-                else if (P.C == 5) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_adapt<5>), sgrid, dim3(kSplatBlock), 0, st, P, B);
-                else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_splat_adapt<4>), sgrid, dim3(kSplatBlock), 0, st, P, B);
-                T.end(st);
-                HIPCHK(hipGetLastError());
-                T.flush();
-                HIPCHK(T.err);
-            }
-            P = Ps;
+        if (pl.rng_carry) arena_release.join();
+        if (pl.do_fill) {
+            arena_release.join();   /* the fill reads the whole pass's adapt_mask: every chunk stream first */
+            if ((s = run_fill(ctx, P, adaptive_lanes)) != AMVPT_OK) return s;
         }
     }
     arena_release.join();
-    if (private_fx) {
-        hipLaunchKernelGGL(k_fixed_resolve, dim3((uint32_t) ((film_floats + 255) / 256)), dim3(256), 0, st, film,
-                           (const unsigned long long *) A.fx, (uint64_t) film_floats);
+    if (pl.private_fx) {
+        hipLaunchKernelGGL(k_fixed_resolve, dim3((uint32_t) ((pl.film_floats + 255) / 256)), dim3(256), 0, st, film,
+                           (const unsigned long long *) A.fx, (uint64_t) pl.film_floats);
         HIPCHK(hipGetLastError());
     }
-    uint64_t overflow_cells = 0;
     if (P.overflow) {
         /* the caller sums the list; a list that ran out of room lost cells: fail loudly */
+        uint64_t overflow_cells = 0;
         HIPCHK(hipMemcpyAsync(&overflow_cells, P.overflow, 8, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         overflow_added = overflow_cells - std::min(overflow_cells, overflow_before);
@@ -4756,56 +4999,18 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
             return AMVPT_ERR_OOM;
         }
     }
-    if (counters) {
-        std::vector<unsigned long long> hsh((size_t) kStats * kStatShards);
-        HIPCHK(hipMemcpyAsync(hsh.data(), dstats, stats_bytes, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        unsigned long long hs[kStats] = {0};
-        for (uint32_t k = 0; k < kStats; ++k)
-            for (uint32_t q = 0; q < kStatShards; ++q) hs[k] += hsh[(size_t) k * kStatShards + q];
-        amvpt_counters &c = *counters;
-        c = amvpt_counters{};
-        c.lanes = span * n_passes;
-        c.passes = n_passes;
-        c.vertices = hs[0];
-        c.reuse_lanes = hs[1];
-        c.visibility_rays = hs[2];
-        c.view_splats = hs[3];
-        c.splat_fallback = hs[4];
-        c.adaptive_lanes = adaptive_lanes;
-        c.shadow_rays = hs[5];
-        c.record_bytes = G > 1 ? 64 + 16 + (diff_rec ? 4 : 32) * (uint64_t) G : 0;
-        c.nonfinite_samples = hs[6];
-        c.negative_samples = hs[7];
-        c.pushed_paths = hs[8];
-        c.film_overflow = overflow_added;   /* this render's cells (renders append to the list) */
-        c.film_range_drops = hs[9];
-        c.primary_record_bytes = hs[10];
-        c.splat_record_bytes = hs[11];
-        c.chunk_lanes = chunk;
-        c.buffer_sets = (uint64_t) n_sets;
-        c.arena_bytes = A.bytes + A.abytes + A.fxbytes + A.cbytes;
-        T.flush();
-        HIPCHK(T.err);
-        for (int k = 0; k < AMVPT_K_COUNT; ++k) { c.kernel_ms[k] = T.ms[k]; c.kernel_launches[k] = T.launches[k]; }
-        c.kernel_ms_primary = T.ms[AMVPT_K_PRIM_HIT] + T.ms[AMVPT_K_PRIM_REQ] + T.ms[AMVPT_K_VIS] +
-                              T.ms[AMVPT_K_MV_PRIMARY] + T.ms[AMVPT_K_RAYGEN];
-        c.kernel_ms_bounce = T.ms[AMVPT_K_EXTEND] + T.ms[AMVPT_K_BOUNCE] + T.ms[AMVPT_K_SHADOW] + T.ms[AMVPT_K_SUFFIX];
-        c.kernel_ms_splat = T.ms[AMVPT_K_SPLAT];
-        c.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
+    if (counters) return read_counters(ctx, A, dstats, adaptive_lanes, overflow_added, t0);
     return AMVPT_OK;
 }
 
 /* amvpt_film_accumulate: window rows into the quilt (one thread per float; a window's floats are
  * distinct quilt floats, so plain adds), then the overflow entries (float atomics: entries repeat) */
-AMVPT_TU_LOCAL __global__ void k_accumulate(float *quilt, uint32_t qw, uint32_t C, const float *win, uint32_t x0,
-                                            uint32_t y0, uint32_t w) {
+__global__ void k_accumulate(float *quilt, uint32_t qw, uint32_t C, const float *win, uint32_t x0, uint32_t y0, uint32_t w) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (i >= w * C) return;
     quilt[((size_t) (y0 + y) * qw + x0) * C + i] += win[(size_t) y * w * C + i];
 }
-AMVPT_TU_LOCAL __global__ void k_overflow_apply(float *quilt, uint64_t n_floats, const uint4 *e, uint64_t n) {
+__global__ void k_overflow_apply(float *quilt, uint64_t n_floats, const uint4 *e, uint64_t n) {
     const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint4 v = e[i];
@@ -4833,14 +5038,14 @@ amvpt_status accumulate_impl(float *quilt, uint32_t qw, uint32_t qh, uint32_t C,
 
 /* amvpt_fixed_accumulate: amvpt_film_accumulate in integers -- plain adds for the window rows (distinct quilt
  * elements), integer atomics for the overflow entries (indices repeat) */
-AMVPT_TU_LOCAL __global__ void k_fixed_accumulate(int64_t *quilt, uint32_t qw, uint32_t C, const int64_t *win, uint32_t x0,
-                                                  uint32_t y0, uint32_t w) {
+__global__ void k_fixed_accumulate(int64_t *quilt, uint32_t qw, uint32_t C, const int64_t *win, uint32_t x0, uint32_t y0,
+                                   uint32_t w) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (i >= w * C) return;
     int64_t *q = quilt + fixed_window_index(qw, C, x0, y0, y, i);
     *q = fixed_sum(*q, win[(size_t) y * w * C + i]);
 }
-AMVPT_TU_LOCAL __global__ void k_fixed_overflow_apply(int64_t *quilt, uint64_t n_elems, const uint64_t *e, uint64_t n) {
+__global__ void k_fixed_overflow_apply(int64_t *quilt, uint64_t n_elems, const uint64_t *e, uint64_t n) {
     const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint64_t idx = e[2 * i];
@@ -4866,7 +5071,7 @@ amvpt_status fixed_accumulate_impl(int64_t *quilt, uint32_t qw, uint32_t qh, uin
 }
 
 /* amvpt_fixed_resolve: one thread per float, fixed_resolve_value's conversion */
-AMVPT_TU_LOCAL __global__ void k_fixed_resolve_to(const int64_t *fx, float *film, uint64_t n, int add) {
+__global__ void k_fixed_resolve_to(const int64_t *fx, float *film, uint64_t n, int add) {
     const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     film[i] = fixed_resolve_value(fx[i], add ? film[i] : 0.f, add);
@@ -4927,5 +5132,5 @@ amvpt_status develop_impl(const float *film, float *out, uint32_t w, uint32_t h,
     return AMVPT_OK;
 }
 
-#endif /* !AMVPT_SHADOW_TU && !AMVPT_GROUP_TU && !AMVPT_KERNEL_PROBE */
+#endif /* AMVPT_MAIN_TU && !AMVPT_KERNEL_PROBE */
 } // namespace amvpt

@@ -245,6 +245,28 @@ def test_mesh_chunk_streams(gpu_ready, amvpt_mod, oracle, variant):
     assert k["k_bin"] > 0 and k["k_extend"] > 0 and k["k_suffix"] == 0
 
 
+def test_mesh_render_after_failed_fill(gpu_ready, amvpt_mod, oracle):
+    """Two renders of the mesh frame's first half that fail in the fill -- after eight main-pass chunks on four chunk
+    streams -- once because the count exchange fails and once because it returns a prefix past the pass's total.
+    Both leave through the arena's release (side streams joined, `done` recorded), so the next render of the whole
+    frame on the same buffer sets is the oracle's, bit for bit."""
+    f = Frame.of(amvpt_mod, oracle, "mesh")
+    half = amvpt_mod.LaneSet(0, f.lanes // 2, 0, 0, 0, 0)
+    assert f.lanes // 2 == 8 * 2048
+
+    def failing(begins, counts):
+        raise RuntimeError("no exchange today")
+
+    def past_total(begins, counts):
+        return [1], sum(counts)   # prefix + count > total
+
+    for exchange, message in ((failing, "adaptive count exchange failed"), (past_total, "inconsistent prefixes")):
+        with pytest.raises(RuntimeError, match=message):
+            f.render(amvpt_mod.OPT_DETERMINISTIC, chunk_lanes=2048, lanes=half, exchange=exchange)
+    cnt, _ = f.exact(chunk_lanes=2048)
+    assert cnt.chunk_lanes == 2048 and cnt.buffer_sets == 4
+
+
 def test_dense_tail_ranges(gpu_ready, amvpt_mod, oracle):
     """dense_all as two lane ranges cut at 3 x 4096 + 7, each with the count exchange and into its own film,
     against the oracle's render of that range with the same exchange: spans of 12295 and 20473 lanes end in tiles
