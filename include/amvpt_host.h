@@ -10,7 +10,9 @@
  *                                           spp, develop, evaluate)  integrator.cpp:30-42,
  *                                           dispatching to MVPathIntegrator::render mvpath.cpp:7-278
  *   amvpt_host_write_exr                 <- Film::write (hdrfilm.cpp, OpenEXR float32)
- *   amvpt_host_display / _write_png      <- Program::display_image(screenshot) + Bitmap::write
+ *   amvpt_host_guides                    <- the aov integrator's position / geo_normal / shape_index
+ *                                           (src/integrators/aov.cpp:245-300; see amvpt_guides.h)
+ *   amvpt_host_display / _write_png     <- Program::display_image(screenshot) + Bitmap::write
  *                                           (src/mitsuba/program.cpp:199-276)
  *   amvpt_host_read_presets / _write_presets <- Preset::import_file / export_file (src/mitsuba/preset.h)
  *   amvpt_host_parse_fov / _perspective_projection
@@ -24,6 +26,7 @@
 
 #include "amvpt.h"
 #include "amvpt_display.h"
+#include "amvpt_guides.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -123,6 +126,26 @@ int amvpt_host_write_exr(const char *path, const float *data, uint32_t width, ui
                          uint32_t channels);
 int amvpt_host_read_exr(const char *path, float *data, uint32_t width, uint32_t height,
                         uint32_t channels);
+
+/*
+ * Interleaved float32 channels (height x width x channels) under caller-given names, e.g. R, G, B, Z, N.X, ..., id.
+ * The file stores them in the byte order of their names, as the format requires; the reader hands them back in the
+ * caller's order, whatever that is.  Names are 1 to 31 bytes and unique; the reader needs the file to hold exactly
+ * the named channels.  amvpt_host_write_exr is the same writer under the names R, G, B[, A] (or Y).
+ */
+int amvpt_host_write_exr_channels(const char *path, const float *data, uint32_t width, uint32_t height,
+                                  uint32_t channels, const char *const *names);
+int amvpt_host_read_exr_channels(const char *path, float *data, uint32_t width, uint32_t height,
+                                 uint32_t channels, const char *const *names);
+
+/*
+ * Guide buffers of a sensor (amvpt_guides.h) on the current device: guides_host receives height x width x 8
+ * float32 (shape index or -1, geometric normal, hit point, view index per quilt pixel), depth_host height x width
+ * float32 (planar depth, +inf on a miss).  Either pointer may be NULL.  Runs on the device scene
+ * amvpt_host_render caches for the current device (created on first use: a guides call after a render creates no
+ * second one, see amvpt_host_render_stats) and does not touch the cached film or image.
+ */
+int amvpt_host_guides(amvpt_host_scene *scene, uint32_t sensor_index, float *guides_host, float *depth_host);
 
 /*
  * The display stage (amvpt_display.h; the reference's front end, src/mitsuba/program.cpp:199-276): render ->

@@ -222,8 +222,81 @@ def hip_lib():
             L.amvpt_fixed_accumulate_host.argtypes = acc
             L.amvpt_fixed_resolve.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u64, ctypes.c_int, ctypes.c_void_p]
             L.amvpt_fixed_resolve_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u64, ctypes.c_int]
+        if hasattr(L, "amvpt_guides_version"):   # include/amvpt_guides.h
+            vp = ctypes.c_void_p
+            L.amvpt_guides_version.restype = u32
+            for fn, args in (("amvpt_guides", [vp, vp, ctypes.POINTER(Params), ctypes.POINTER(u32 * 4), vp, vp]),
+                             ("amvpt_guide_depth", [vp, vp, u32, u64, vp, vp]),
+                             ("amvpt_guide_depth_host", [vp, vp, u32, u64, vp]),
+                             ("amvpt_guide_depth_range", [vp, u64, ctypes.POINTER(f32 * 2), vp]),
+                             ("amvpt_guide_depth_range_host", [vp, u64, ctypes.POINTER(f32 * 2)]),
+                             ("amvpt_depth8", [vp, u32, u32, f32, f32, vp, vp]),
+                             ("amvpt_depth8_host", [vp, u32, u32, f32, f32, vp])):
+                getattr(L, fn).restype = ctypes.c_int
+                getattr(L, fn).argtypes = args
         _hip = L
     return _hip
+
+
+def guides_version():
+    """AMVPT_GUIDES_VERSION of the loaded library (include/amvpt_guides.h)."""
+    return hip_lib().amvpt_guides_version()
+
+
+def guide_depth(guides_ptr, views, n_views, n_pixels, depth_ptr, stream=None):
+    """amvpt_guide_depth over device pointers: guide records -> planar depth (+inf on a miss), ordered on `stream`.
+    `views` is the host ViewDesc table."""
+    L = hip_lib()
+    _check(L.amvpt_guide_depth(ctypes.c_void_p(guides_ptr), views, n_views, n_pixels,
+                               ctypes.c_void_p(depth_ptr), ctypes.c_void_p(stream or 0)), L)
+
+
+def guide_depth_host(guides, views, n_views):
+    """amvpt_guide_depth_host over numpy: (..., 8) float32 guide records -> (...) float32 planar depth."""
+    L = hip_lib()
+    g = np.ascontiguousarray(guides, dtype=np.float32)
+    if g.ndim < 1 or g.shape[-1] != 8:
+        raise ValueError("guide_depth_host: (..., 8) guide records are needed")
+    out = np.empty(g.shape[:-1], dtype=np.float32)
+    _check(L.amvpt_guide_depth_host(g.ctypes.data, views, n_views, out.size, out.ctypes.data), L)
+    return out
+
+
+def guide_depth_range(depth_ptr, n, stream=None):
+    """amvpt_guide_depth_range: (min, max) over the finite values of the device depth plane; (0, 0) when there is
+    none.  Synchronises `stream`."""
+    L = hip_lib()
+    nf = (f32 * 2)()
+    _check(L.amvpt_guide_depth_range(ctypes.c_void_p(depth_ptr), n, ctypes.byref(nf), ctypes.c_void_p(stream or 0)), L)
+    return np.float32(nf[0]), np.float32(nf[1])
+
+
+def guide_depth_range_host(depth):
+    """amvpt_guide_depth_range_host over a numpy depth plane."""
+    L = hip_lib()
+    d = np.ascontiguousarray(depth, dtype=np.float32)
+    nf = (f32 * 2)()
+    _check(L.amvpt_guide_depth_range_host(d.ctypes.data if d.size else None, d.size, ctypes.byref(nf)), L)
+    return np.float32(nf[0]), np.float32(nf[1])
+
+
+def depth8(depth_ptr, width, height, near, far, out_ptr, stream=None):
+    """amvpt_depth8 over device pointers: depth plane -> height x width x 3 uint8, nearer brighter, a miss 0."""
+    L = hip_lib()
+    _check(L.amvpt_depth8(ctypes.c_void_p(depth_ptr), width, height, float(near), float(far), ctypes.c_void_p(out_ptr),
+                          ctypes.c_void_p(stream or 0)), L)
+
+
+def depth8_host(depth, near, far):
+    """amvpt_depth8_host over numpy: (H, W) float32 depth -> (H, W, 3) uint8."""
+    L = hip_lib()
+    d = np.ascontiguousarray(depth, dtype=np.float32)
+    if d.ndim != 2:
+        raise ValueError("depth8_host: an (H, W) depth plane is needed")
+    h, w = d.shape
+    out = np.empty((h, w, 3), dtype=np.uint8)
+    _check(L.amvpt_depth8_host(d.ctypes.data if d.size else None, w, h, float(near), float(far), out.ctypes.data), L)
+    return out
 
 
 def fixed_version():
@@ -317,6 +390,11 @@ def host_lib():
         L.amvpt_host_integrator_string.restype = ctypes.c_char_p
         L.amvpt_host_write_exr.argtypes = [ctypes.c_char_p, ctypes.c_void_p, u32, u32, u32]
         L.amvpt_host_read_exr.argtypes = [ctypes.c_char_p, ctypes.c_void_p, u32, u32, u32]
+        if hasattr(L, "amvpt_host_guides"):   # older variant builds (AMVPT_LIB_DIR A/B runs) lack the guide buffers
+            L.amvpt_host_guides.argtypes = [ctypes.c_void_p, u32, ctypes.c_void_p, ctypes.c_void_p]
+            names = ctypes.POINTER(ctypes.c_char_p)
+            L.amvpt_host_write_exr_channels.argtypes = [ctypes.c_char_p, ctypes.c_void_p, u32, u32, u32, names]
+            L.amvpt_host_read_exr_channels.argtypes = [ctypes.c_char_p, ctypes.c_void_p, u32, u32, u32, names]
         L.amvpt_host_parse_fov.argtypes = [f64, ctypes.c_char_p, ctypes.c_char_p, f64]
         L.amvpt_host_parse_fov.restype = f64
         L.amvpt_host_perspective_projection.argtypes = [ctypes.POINTER(ctypes.c_int)] * 3 + [f32, f32, f32,
@@ -554,6 +632,75 @@ def read_exr(path, width, height, channels):
     return out
 
 
+def _name_array(names):
+    enc = [str(n).encode() for n in names]
+    return (ctypes.c_char_p * max(1, len(enc)))(*enc), len(enc)
+
+
+def write_exr_channels(path, data, names):
+    """(H, W, C) float32 -> an OpenEXR file with one float32 channel per name (amvpt_host_write_exr_channels).
+    Names are 1 to 31 bytes and unique; the file stores the channels in the byte order of their names."""
+    img = np.ascontiguousarray(data, dtype=np.float32)
+    if img.ndim != 3:
+        raise ValueError("write_exr_channels: an (H, W, C) array is needed")
+    h, w, c = img.shape
+    arr, n = _name_array(names)
+    if n != c:
+        raise ValueError("write_exr_channels: %d names for %d channels" % (n, c))
+    L = host_lib()
+    _check(L.amvpt_host_write_exr_channels(str(path).encode(), img.ctypes.data_as(ctypes.c_void_p), w, h, c, arr), L)
+
+
+def read_exr_channels(path, width, height, names):
+    """The named float32 channels of a file write_exr_channels wrote -> (height, width, len(names)), in the order
+    of `names` (amvpt_host_read_exr_channels)."""
+    arr, n = _name_array(names)
+    out = np.zeros((height, width, n), dtype=np.float32)
+    L = host_lib()
+    _check(L.amvpt_host_read_exr_channels(str(path).encode(), out.ctypes.data_as(ctypes.c_void_p), width, height, n,
+                                          arr), L)
+    return out
+
+
+def _host_guides(scene, sensor, want_guides, want_depth):
+    w, h, _, _ = scene.film_info(sensor)
+    g = np.zeros((h, w, 8), dtype=np.float32) if want_guides else None
+    z = np.zeros((h, w), dtype=np.float32) if want_depth else None
+    _check(scene._lib.amvpt_host_guides(scene._h, sensor, g.ctypes.data if g is not None else None,
+                                        z.ctypes.data if z is not None else None), scene._lib)
+    return g, z
+
+
+def guides(scene, sensor=0):
+    """Guide records of every quilt pixel -> (H, W, 8) float32: shape index (-1: miss), geometric normal, hit
+    point, view index, through the pixel centre (amvpt_host_guides; on the device scene render() caches)."""
+    return _host_guides(scene, sensor, True, False)[0]
+
+
+def depth(scene, sensor=0):
+    """Planar depth of every quilt pixel -> (H, W) float32: the camera-space z of the primary hit in the pixel's
+    own view, +inf on a miss (amvpt_host_guides)."""
+    return _host_guides(scene, sensor, False, True)[1]
+
+
+GUIDE_CHANNELS = ("Z", "N.X", "N.Y", "N.Z", "P.X", "P.Y", "P.Z", "id", "view")
+
+
+def write_guides_exr(path, image, guides, depth):
+    """One OpenEXR file with the developed image (H, W, 3 or 4) and its guide buffers: channels R, G, B[, A], Z,
+    N.X, N.Y, N.Z, P.X, P.Y, P.Z, id, view.  id = shape index + 1 with 0 the background, the convention of the
+    reference's `shape_index` AOV (aov.cpp:231-235)."""
+    img = np.asarray(image, dtype=np.float32)
+    g = np.asarray(guides, dtype=np.float32)
+    z = np.asarray(depth, dtype=np.float32)
+    if img.ndim != 3 or img.shape[2] not in (3, 4):
+        raise ValueError("write_guides_exr: an (H, W, 3 or 4) image is needed")
+    if g.shape != img.shape[:2] + (8,) or z.shape != img.shape[:2]:
+        raise ValueError("write_guides_exr: guides must be (H, W, 8) and depth (H, W) of the image's size")
+    planes = np.concatenate([img, z[..., None], g[..., 1:7], g[..., 0:1] + np.float32(1.0), g[..., 7:8]], axis=2)
+    write_exr_channels(path, planes, ("R", "G", "B", "A")[:img.shape[2]] + GUIDE_CHANNELS)
+
+
 def parse_fov(fov=0.0, fov_axis=None, focal_length=None, aspect=1.0):
     L = host_lib()
     r = L.amvpt_host_parse_fov(float(fov), fov_axis.encode() if fov_axis else None,
@@ -650,6 +797,14 @@ class DeviceScene:
         _check(self._lib.amvpt_render_records(self.h, views_ptr, ctypes.byref(params), pass_index, lane_begin,
                                               lane_end, ctypes.c_void_p(film_ptr), ctypes.c_void_p(records_ptr),
                                               ctypes.c_void_p(stream)), self._lib)
+
+    def guides(self, views_ptr, params, out_ptr, rect=None, stream=None):
+        """amvpt_guides: the guide record (shape index or -1, geometric normal, hit point, view index; 8 float32)
+        of every pixel of `rect` = (x0, y0, w, h) of the quilt crop (None: all of it) into the device buffer at
+        `out_ptr` (h * w * 8 floats, 16-byte aligned), ordered on `stream`."""
+        r = ctypes.byref((u32 * 4)(*[int(v) for v in rect])) if rect is not None else None
+        _check(self._lib.amvpt_guides(self.h, views_ptr, ctypes.byref(params), r, ctypes.c_void_p(out_ptr or 0),
+                                      ctypes.c_void_p(stream or 0)), self._lib)
 
     def __del__(self):
         if getattr(self, "h", None):

@@ -5,7 +5,8 @@ src/mitsuba/program.cpp:199-276 with the presets of src/mitsuba/preset.h).
 
 `srgb8`, `interlace` and `views` run the host entries over numpy arrays and need no device;
 `srgb8_device` / `interlace_device` launch the kernels over device pointers; `display` renders a scene and
-runs the whole stage on the device, downloading the display image once.
+runs the whole stage on the device, downloading the display image once.  `depth_quilt` is the 8-bit depth
+quilt of a scene (include/amvpt_guides.h), the RGB-D companion of the sRGB quilt.
 """
 import ctypes
 
@@ -183,6 +184,19 @@ def display(scene, preset=None, size=(1280, 720), quilt=False, nearest=False, se
                                              ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(stream or 0),
                                              ctypes.byref(cnt)), H)
     return out
+
+
+def depth_quilt(scene, sensor=0, near=None, far=None):
+    """The depth quilt of `scene` for an RGB-D display -> (H, W, 3) uint8, nearer brighter, a miss 0: the planar
+    depth of every quilt pixel (amvpt.depth: k_guides and k_guide_depth on the device scene render() caches)
+    coded by amvpt.depth8_host.  A bound left None comes from the frame itself (amvpt.guide_depth_range_host:
+    the nearest hit 255, the farthest 0).  The host forms are bit-identical to the device entries."""
+    z = amvpt.depth(scene, sensor)
+    if near is None or far is None:
+        lo, hi = amvpt.guide_depth_range_host(z)
+        near = lo if near is None else near
+        far = hi if far is None else far
+    return amvpt.depth8_host(z, near, far)
 
 
 def read_presets(path):

@@ -2524,6 +2524,33 @@ __global__ void __launch_bounds__(256) k_prim_hit(KParams P, const DScene *Sp, c
     }
 }
 
+#ifdef AMVPT_MAIN_TU
+/*
+ * Guide buffers (include/amvpt_guides.h): the primary hit through the centre of pixel i of a w-pixel-wide rectangle
+ * at (x0, y0) of the quilt crop, as 8 floats -- shape index (-1: miss), geometric normal, hit point, view index.
+ * k_prim_hit's pieces without a sampler: sample_ray_idx at the pixel centre (aperture sample (.5, .5): a thin lens
+ * traces from its centre), the closest-hit walk of the render's coherent rays, compute_si.  The wave-uniform
+ * instance reads the BVH with scalar loads and stages nothing (as k_prim_hit_req); the per-lane one stages it where
+ * it fits (as k_prim_hit).  Two float4 stores per thread; no atomics.
+ */
+template <bool kUni>
+__global__ void __launch_bounds__(256) k_guides(KParams P, const DScene *Sp, const DView *V, uint32_t x0, uint32_t y0,
+                                                uint32_t w, uint32_t n, float4 *__restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    DScene S = *Sp;
+    SceneRef sc = stage_scene<false, !kUni>(S, lds, P.trav_mode);
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t ry = i / w, x = x0 + (i - ry * w), y = y0 + ry;
+    uint32_t index = 0;
+    const Ray ray = sample_ray_idx(P, V, fmadd((float) (x + P.off_x) + .5f, P.inv_w, P.adj_ox),
+                                   fmadd((float) (y + P.off_y) + .5f, P.inv_h, P.adj_oy), index);
+    const SI si = compute_si(sc, ray, trace_closest<kUni>(sc, ray));
+    out[2 * (size_t) i] = make_float4(si.valid() ? (float) si.shape : -1.f, si.n.x, si.n.y, si.n.z);
+    out[2 * (size_t) i + 1] = make_float4(si.p.x, si.p.y, si.p.z, (float) index);
+}
+#endif
+
 /* k_prim_req's body for lane-order thread i: the primary vertex (pr, hit) -> visibility requests */
 template <int G, bool kTab, bool kDiff>
 AD void prim_requests(const KParams &P, const SceneRef &sc, const DScene &S, const DView *V, const Bufs &B, uint32_t i,
@@ -4194,6 +4221,31 @@ static amvpt_status plan_lanes(const RenderCall &c, RenderPlan &pl) {
     return AMVPT_OK;
 }
 
+/* the raygen constants: what maps a film position to sample_ray_idx's argument and what sample_ray_idx reads.  A
+ * render (plan_params) and amvpt_guides (guides_impl) both take them from here, so that they are the same floats */
+static void plan_raygen(const amvpt_params &Pp, const amvpt_view_desc *views, KParams &P) {
+    P.W = Pp.film_width; P.H = Pp.film_height;
+    P.multisensor = Pp.multisensor; P.batch = Pp.batch; P.n_views = Pp.n_views;
+    /* grid: its first sub-sensor decides (grid.cpp:228); batch: any child (batch.cpp:127) */
+    P.needs_ap = 0;
+    for (uint32_t v = 0; v < (Pp.multisensor && Pp.batch ? Pp.n_views : 1u); ++v)
+        P.needs_ap |= views[v].type == AMVPT_CAMERA_THINLENS ? 1u : 0u;
+    P.gx = Pp.grid_x ? Pp.grid_x : 1; P.gy = Pp.grid_y ? Pp.grid_y : 1;
+    P.rev_x = Pp.reverse_x; P.rev_y = Pp.reverse_y;
+    P.inv_w = 1.f / (float) P.W;
+    P.inv_h = 1.f / (float) P.H;
+    P.off_x = Pp.crop_offset_x; P.off_y = Pp.crop_offset_y;
+    P.adj_ox = -(float) P.off_x * P.inv_w;   /* -ScalarVector2f(crop_offset) * scale */
+    P.adj_oy = -(float) P.off_y * P.inv_h;
+}
+
+/* the walk of the coherent rays (primary, visibility): wave-uniform on every BVH in automatic mode (see
+ * launch_primary), else per lane with the BVH staged in `lds_bvh` bytes of LDS where it fits (0: device memory) */
+struct CoherentWalk { bool uni; size_t lds_bvh; };
+static CoherentWalk coherent_walk(const amvpt_scene *scene, uint32_t trav) {
+    return CoherentWalk{scene_uniform(scene->dev.n_nodes, trav) || trav == 0u, scene_lds_bytes(scene->dev, trav)};
+}
+
 /* the kernel parameters the call decides */
 static void plan_params(const RenderCall &c, RenderPlan &pl) {
     const amvpt_params &Pp = c.Pp;
@@ -4201,7 +4253,8 @@ static void plan_params(const RenderCall &c, RenderPlan &pl) {
     const amvpt_film_window &fwin = c.fwin;
     const uint32_t spp_pp = pl.spp_pp, QW = Pp.film_width;
     KParams &P = pl.P;
-    P.W = Pp.film_width; P.H = Pp.film_height; P.C = Pp.film_alpha ? 5 : 4;
+    plan_raygen(Pp, c.views, P);
+    P.C = Pp.film_alpha ? 5 : 4;
     P.spp_pp = spp_pp;
     uint32_t log_spp = 0;
     while ((1u << log_spp) < spp_pp) ++log_spp;
@@ -4210,13 +4263,6 @@ static void plan_params(const RenderCall &c, RenderPlan &pl) {
     P.max_depth = Pp.max_depth; P.rr_depth = Pp.rr_depth;
     P.sa_mis = Pp.sa_mis; P.fast_mis = Pp.fast_mis; P.debug = Pp.debug; P.n_adapt = pl.n_adapt;
     P.G = pl.G;
-    P.multisensor = Pp.multisensor; P.batch = Pp.batch; P.n_views = Pp.n_views;
-    /* grid: its first sub-sensor decides (grid.cpp:228); batch: any child (batch.cpp:127) */
-    P.needs_ap = 0;
-    for (uint32_t v = 0; v < (Pp.multisensor && Pp.batch ? Pp.n_views : 1u); ++v)
-        P.needs_ap |= c.views[v].type == AMVPT_CAMERA_THINLENS ? 1u : 0u;
-    P.gx = Pp.grid_x ? Pp.grid_x : 1; P.gy = Pp.grid_y ? Pp.grid_y : 1;
-    P.rev_x = Pp.reverse_x; P.rev_y = Pp.reverse_y;
     /* quilt tile pitch of reprojected views: film->size() / grid (mvpath_multi.h:62), the full film */
     const uint32_t fullW = Pp.full_width ? Pp.full_width : P.W, fullH = Pp.full_height ? Pp.full_height : P.H;
     P.sres_x = fullW / P.gx; P.sres_y = fullH / P.gy;
@@ -4224,11 +4270,6 @@ static void plan_params(const RenderCall &c, RenderPlan &pl) {
     P.coalesce_single = spp_pp >= 4;
     P.path_box_pos = (!pl.is_mv && P.box) ? 1 : 0;
     P.is_mvpath = pl.is_mv;
-    P.inv_w = 1.f / (float) P.W;
-    P.inv_h = 1.f / (float) P.H;
-    P.off_x = Pp.crop_offset_x; P.off_y = Pp.crop_offset_y;
-    P.adj_ox = -(float) P.off_x * P.inv_w;   /* -ScalarVector2f(crop_offset) * scale */
-    P.adj_oy = -(float) P.off_y * P.inv_h;
     P.nc_ox = (float) (-(int) P.off_x) - .5f;
     P.nc_oy = (float) (-(int) P.off_y) - .5f;
     P.adapt_w = 1.f / (float) (pl.n_adapt + 1);
@@ -4289,7 +4330,8 @@ static void plan_walks(const RenderCall &c, RenderPlan &pl) {
     const bool uni = scene_uniform(scene->dev.n_nodes, trav);
     /* the coherent primary and visibility rays walk wave-uniformly on every BVH in automatic mode
      * (see launch_primary); the incoherent suffix rays keep the per-lane walk */
-    pl.uni_coh = uni || trav == 0u;
+    const CoherentWalk cw = coherent_walk(scene, trav);
+    pl.uni_coh = cw.uni;
     /* suffix walk: brute force for tiny scenes in auto mode */
     pl.walk = uni ? WALK_UNI : scene->has_spheres ? WALK_LANE : scene->bvh_tri_only ? WALK_LANE_TRI : WALK_LANE_NS;
     if (uni && trav == 0u && scene->dev.n_prims <= kBrutePrims) pl.walk = scene->has_spheres ? WALK_BRUTE : WALK_BRUTE_NS;
@@ -4299,7 +4341,7 @@ static void plan_walks(const RenderCall &c, RenderPlan &pl) {
      * AMVPT_OPT_WAVEFRONT_SUFFIX keeps the per-depth k_extend / k_bounce wavefronts) */
     pl.fuse_suffix = pl.fuse_nee && !(opts.flags & AMVPT_OPT_WAVEFRONT_SUFFIX);
     /* ray binning (k_bin_sort) for the per-lane suffix walks of BVHs read from device memory */
-    pl.lds_ext = scene_lds_bytes(scene->dev, trav);
+    pl.lds_ext = cw.lds_bvh;
     pl.lane_walk = is_lane_walk(pl.walk) && !pl.fuse_suffix && pl.lds_ext == 0u;
     pl.bin_ext = pl.lane_walk && !(opts.flags & AMVPT_OPT_NO_BINNING);   /* the extension rays (k_extend) */
     pl.bin_nee = pl.bin_ext && !pl.fuse_nee;                              /* the NEE rays (k_shadow) */
@@ -5000,6 +5042,68 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
         }
     }
     if (counters) return read_counters(ctx, A, dstats, adaptive_lanes, overflow_added, t0);
+    return AMVPT_OK;
+}
+
+/*
+ * amvpt_guides: k_guides over a pixel rectangle of the quilt crop.  The call is checked as a whole-frame render is
+ * (plan_lanes), the raygen constants and the walk tier are the render's (plan_raygen, coherent_walk), and the view
+ * table goes where a render puts it: the head of the device's lane arena, taken under its lock.
+ */
+amvpt_status guides_impl(amvpt_scene *scene, const amvpt_view_desc *views, const amvpt_params *params,
+                         const uint32_t *rect, float *out, void *stream) {
+    if (!scene) { set_error("amvpt_guides: null scene"); return AMVPT_ERR_INVALID; }
+    if (!views) { set_error("amvpt_guides: null views"); return AMVPT_ERR_INVALID; }
+    if (!params) { set_error("amvpt_guides: null params"); return AMVPT_ERR_INVALID; }
+    if (!out) { set_error("amvpt_guides: null out_device"); return AMVPT_ERR_INVALID; }
+    if ((uintptr_t) out & 15u) { set_error("amvpt_guides: out_device must be 16-byte aligned (float4 stores)"); return AMVPT_ERR_INVALID; }
+    hipStream_t st = (hipStream_t) stream;
+    amvpt_lane_set lanes{};
+    lanes.lane_end = UINT64_MAX;
+    amvpt_film_window fwin{};
+    fwin.width = params->film_width;
+    fwin.height = params->film_height;
+    amvpt_render_opts opts{};
+    opts.traversal = g_traversal;
+    const RenderCall call{scene, views, *params, lanes, fwin, st, opts, nullptr, nullptr, 0, false};
+    RenderPlan pl;
+    pl.P = KParams{};
+    amvpt_status s = plan_lanes(call, pl);
+    if (s != AMVPT_OK) return s;
+    const uint32_t QW = params->film_width, QH = params->film_height;
+    const uint32_t x0 = rect ? rect[0] : 0u, y0 = rect ? rect[1] : 0u, w = rect ? rect[2] : QW, h = rect ? rect[3] : QH;
+    if (w == 0 || h == 0) { set_error("amvpt_guides: rect has zero area"); return AMVPT_ERR_INVALID; }
+    if ((uint64_t) x0 + w > QW || (uint64_t) y0 + h > QH) {
+        set_error("amvpt_guides: rect (" + std::to_string(x0) + ", " + std::to_string(y0) + ", " + std::to_string(w) + ", " +
+                  std::to_string(h) + ") outside the quilt crop of " + std::to_string(QW) + " x " + std::to_string(QH));
+        return AMVPT_ERR_INVALID;
+    }
+    /* one launch covers the rectangle, and HIP refuses a grid of 2^32 threads or more */
+    if ((uint64_t) w * h > 0xffffff00ull) { set_error("amvpt_guides: rect above 2^32 - 256 pixels"); return AMVPT_ERR_INVALID; }
+    const uint32_t n = w * h;
+    KParams &P = pl.P;
+    plan_raygen(*params, views, P);
+    P.trav_mode = opts.traversal;
+    const CoherentWalk cw = coherent_walk(scene, opts.traversal);
+
+    const std::vector<DView> hv = host_views(call);
+    const size_t views_bytes = ((hv.size() * sizeof(DView)) + 255) & ~(size_t) 255;
+    int dev = 0;
+    HIPCHK(hipGetDevice(&dev));
+    DevArena &A = dev_arena(dev);
+    std::unique_lock<std::mutex> arena_lock(A.mu);
+    if (!A.done) HIPCHK(hipEventCreateWithFlags(&A.done, hipEventDisableTiming));
+    if (A.pending && A.last != st) HIPCHK(hipStreamWaitEvent(st, A.done, 0));
+    ArenaRelease arena_release{A, st, 0};
+    if ((s = arena_reserve(A, A.base, A.bytes, views_bytes, "lane arena")) != AMVPT_OK) return s;
+    DView *dviews = (DView *) A.base;
+    HIPCHK(hipMemcpyAsync(dviews, hv.data(), hv.size() * sizeof(DView), hipMemcpyHostToDevice, st));
+    const DScene *dS = (const DScene *) scene->dev_scene_struct;
+    const dim3 grid((n + 255u) / 256u);
+    float4 *o4 = reinterpret_cast<float4 *>(out);
+    if (cw.uni) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_guides<true>), grid, dim3(256), 0, st, P, dS, dviews, x0, y0, w, n, o4);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_guides<false>), grid, dim3(256), cw.lds_bvh, st, P, dS, dviews, x0, y0, w, n, o4);
+    HIPCHK(hipGetLastError());
     return AMVPT_OK;
 }
 

@@ -38,6 +38,9 @@ amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const
 amvpt_status fixed_accumulate_impl(int64_t *quilt, uint32_t qw, uint32_t qh, uint32_t C, const int64_t *win, uint32_t x0,
                                    uint32_t y0, uint32_t w, uint32_t h, const uint64_t *ov, uint64_t n_ov, void *stream);
 amvpt_status fixed_resolve_impl(const int64_t *fixed, float *film, uint64_t n, int add, void *stream);
+/* amvpt_guides.h: k_guides over rect (x0, y0, w, h; null: the whole quilt crop) -> out (device, 8 floats per pixel) */
+amvpt_status guides_impl(amvpt_scene *scene, const amvpt_view_desc *views, const amvpt_params *params,
+                         const uint32_t *rect, float *out, void *stream);
 amvpt_status develop_impl(const float *film, float *out, uint32_t w, uint32_t h, uint32_t alpha, void *stream);
 amvpt_status release_impl(int device);
 amvpt_status rfilter_eval_impl(const amvpt_params *params, const float *x, uint32_t n, float *out, float *radius);

@@ -1,8 +1,10 @@
 /*
  * exr.cpp -- OpenEXR writer/reader for developed films (float32, uncompressed
- * scanlines, channels Y or R,G,B[,A]).  Replaces the reference's Bitmap/OpenEXR path
+ * scanlines, channels Y or R,G,B[,A]) and for interleaved float32 channels with caller-given names
+ * (guide buffers: Z, N.X, ..., id, view).  Replaces the reference's Bitmap/OpenEXR path
  * used by Film::write (src/films/hdrfilm.cpp:420-546, OpenEXR submodule not vendored).
  */
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -26,30 +28,47 @@ void attr(std::vector<uint8_t> &b, const char *name, const char *type, const std
     put_i32(b, (int32_t) v.size());
     b.insert(b.end(), v.begin(), v.end());
 }
-const char *kNames1[] = {"Y"};
-const char *kNames3[] = {"B", "G", "R"};
-const char *kNames4[] = {"A", "B", "G", "R"};
-/* channel index in the interleaved (R,G,B[,A]) source for each sorted EXR channel */
-const int kSrc1[] = {0};
-const int kSrc3[] = {2, 1, 0};
-const int kSrc4[] = {3, 2, 1, 0};
-const char *name_of(uint32_t c, uint32_t k) { return c == 1 ? kNames1[k] : c == 3 ? kNames3[k] : kNames4[k]; }
-int src_of(uint32_t c, uint32_t k) { return c == 1 ? kSrc1[k] : c == 3 ? kSrc3[k] : kSrc4[k]; }
+const char *const kNames1[] = {"Y"};
+const char *const kNames3[] = {"R", "G", "B"};
+const char *const kNames4[] = {"R", "G", "B", "A"};
 int fail(const std::string &msg) {
     amvpt_host_set_error(msg);
     return -1;
 }
-} // namespace
 
-extern "C" int amvpt_host_write_exr(const char *path, const float *data, uint32_t w, uint32_t h, uint32_t c) {
-    if (c != 1 && c != 3 && c != 4) return fail("write_exr: channel count must be 1, 3 or 4");
-    if (!w || !h) return fail("write_exr: empty image");
+/* the caller's channel names: 1 to 31 bytes (the format's limit) and unique; order[k] = the source channel of the
+ * k-th channel in the byte order of the names, the order the format stores them in */
+int check_names(const char *who, uint32_t c, const char *const *names, std::vector<uint32_t> &order) {
+    const std::string w = std::string(who) + ": ";
+    if (c == 0) return fail(w + "no channels");
+    if (!names) return fail(w + "null names");
+    for (uint32_t k = 0; k < c; ++k) {
+        if (!names[k]) return fail(w + "channel " + std::to_string(k) + " has a null name");
+        const size_t len = std::strlen(names[k]);
+        if (len == 0) return fail(w + "channel " + std::to_string(k) + " has an empty name");
+        if (len > 31) return fail(w + "channel " + std::to_string(k) + " (\"" + names[k] + "\") has a name longer than 31 bytes");
+        for (uint32_t j = 0; j < k; ++j)
+            if (std::strcmp(names[j], names[k]) == 0)
+                return fail(w + "channel " + std::to_string(k) + " repeats the name \"" + names[k] + "\" of channel " + std::to_string(j));
+    }
+    order.resize(c);
+    for (uint32_t k = 0; k < c; ++k) order[k] = k;
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return std::strcmp(names[a], names[b]) < 0; });
+    return 0;
+}
+
+int write_channels(const char *who, const char *path, const float *data, uint32_t w, uint32_t h, uint32_t c,
+                   const char *const *names) {
+    std::vector<uint32_t> order;
+    if (int rc = check_names(who, c, names, order)) return rc;
+    if (!path || !data) return fail(std::string(who) + ": null argument");
+    if (!w || !h) return fail(std::string(who) + ": empty image");
     std::vector<uint8_t> b;
     put_i32(b, 20000630);
     put_i32(b, 2);
     std::vector<uint8_t> v;
     for (uint32_t k = 0; k < c; ++k) {
-        put_str(v, name_of(c, k));
+        put_str(v, names[order[k]]);
         put_i32(v, 2);                 /* FLOAT */
         uint8_t lin[4] = {0, 0, 0, 0}; /* pLinear + reserved */
         put_bytes(v, lin, 4);
@@ -86,53 +105,113 @@ extern "C" int amvpt_host_write_exr(const char *path, const float *data, uint32_
         put_i32(b, (int32_t) y);
         put_i32(b, (int32_t) line_bytes);
         for (uint32_t k = 0; k < c; ++k) {
-            int src = src_of(c, k);
+            const uint32_t src = order[k];
             for (uint32_t x = 0; x < w; ++x) line[(size_t) k * w + x] = data[((size_t) y * w + x) * c + src];
         }
         put_bytes(b, line.data(), line_bytes);
     }
     FILE *f = std::fopen(path, "wb");
-    if (!f) return fail(std::string("write_exr: cannot open ") + path);
+    if (!f) return fail(std::string(who) + ": cannot open " + path);
     size_t n = std::fwrite(b.data(), 1, b.size(), f);
     std::fclose(f);
-    return n == b.size() ? 0 : fail(std::string("write_exr: short write to ") + path);
+    return n == b.size() ? 0 : fail(std::string(who) + ": short write to " + path);
 }
 
-/* Reads files produced by amvpt_host_write_exr (same layout). */
-extern "C" int amvpt_host_read_exr(const char *path, float *data, uint32_t w, uint32_t h, uint32_t c) {
-    if (c != 1 && c != 3 && c != 4) return fail("read_exr: channel count must be 1, 3 or 4");
+/* Reads files produced by write_channels (same layout): every named channel must be one of the file's float32
+ * channels, whose count must be c */
+int read_channels(const char *who, const char *path, float *data, uint32_t w, uint32_t h, uint32_t c,
+                  const char *const *names) {
+    const std::string wh = std::string(who) + ": ";
+    std::vector<uint32_t> order;
+    if (int rc = check_names(who, c, names, order)) return rc;
+    if (!path || !data) return fail(wh + "null argument");
     FILE *f = std::fopen(path, "rb");
-    if (!f) return fail(std::string("read_exr: cannot open ") + path);
+    if (!f) return fail(wh + "cannot open " + path);
     std::vector<uint8_t> b;
     uint8_t buf[65536];
     size_t n;
     while ((n = std::fread(buf, 1, sizeof(buf), f)) > 0) b.insert(b.end(), buf, buf + n);
     std::fclose(f);
-    if (b.size() < 8) return fail("read_exr: truncated file");
+    if (b.size() < 8) return fail(wh + "truncated file");
     int32_t magic;
     std::memcpy(&magic, b.data(), 4);
-    if (magic != 20000630) return fail("read_exr: not an OpenEXR file");
+    if (magic != 20000630) return fail(wh + "not an OpenEXR file");
+    b.push_back(0);   /* a terminator for the header's strings, whatever the file holds */
+    const size_t end = b.size() - 1;
+    std::vector<std::string> file_names;
+    bool have_list = false;
     size_t p = 8;
-    while (p < b.size() && b[p] != 0) {
+    while (p < end && b[p] != 0) {
         std::string name((const char *) &b[p]);
         p += name.size() + 1;
+        if (p >= end) return fail(wh + "truncated header");
         std::string type((const char *) &b[p]);
         p += type.size() + 1;
+        if (p + 4 > end) return fail(wh + "truncated header");
         int32_t sz;
         std::memcpy(&sz, &b[p], 4);
-        p += 4 + (size_t) sz;
+        p += 4;
+        if (sz < 0 || p + (size_t) sz > end) return fail(wh + "truncated header");
+        if (name == "channels") {
+            have_list = true;
+            size_t q = p;
+            const size_t qe = p + (size_t) sz;
+            while (q < qe && b[q] != 0) {
+                std::string ch((const char *) &b[q]);
+                q += ch.size() + 1;
+                if (q + 16 > qe) return fail(wh + "truncated channel list");
+                int32_t pixel_type;
+                std::memcpy(&pixel_type, &b[q], 4);
+                if (pixel_type != 2) return fail(wh + "channel \"" + ch + "\" is not float32");
+                q += 16;
+                file_names.push_back(ch);
+            }
+        }
+        p += (size_t) sz;
+    }
+    if (!have_list) return fail(wh + "no channel list");
+    if (file_names.size() != c)
+        return fail(wh + "the file holds " + std::to_string(file_names.size()) + " channels, not " + std::to_string(c));
+    /* the file's k-th channel -> the caller's channel of that name */
+    std::vector<uint32_t> dst(c);
+    for (uint32_t k = 0; k < c; ++k) {
+        uint32_t j = 0;
+        while (j < c && file_names[k] != names[j]) ++j;
+        if (j == c) return fail(wh + "the file's channel \"" + file_names[k] + "\" is not among the names asked for");
+        dst[k] = j;
     }
     p += 1 + 8ull * h;
     const size_t line_bytes = (size_t) w * c * 4;
     for (uint32_t y = 0; y < h; ++y) {
-        if (p + 8 + line_bytes > b.size()) return fail("read_exr: truncated scanline data");
+        if (p + 8 + line_bytes > end) return fail(wh + "truncated scanline data");
         p += 8;
-        const float *line = (const float *) &b[p];
-        for (uint32_t k = 0; k < c; ++k) {
-            int dst = src_of(c, k);
-            for (uint32_t x = 0; x < w; ++x) data[((size_t) y * w + x) * c + dst] = line[(size_t) k * w + x];
-        }
+        for (uint32_t k = 0; k < c; ++k)
+            for (uint32_t x = 0; x < w; ++x)
+                std::memcpy(&data[((size_t) y * w + x) * c + dst[k]], &b[p + ((size_t) k * w + x) * 4], 4);
         p += line_bytes;
     }
     return 0;
+}
+const char *const *rgb_names(uint32_t c) { return c == 1 ? kNames1 : c == 3 ? kNames3 : kNames4; }
+} // namespace
+
+extern "C" int amvpt_host_write_exr(const char *path, const float *data, uint32_t w, uint32_t h, uint32_t c) {
+    if (c != 1 && c != 3 && c != 4) return fail("write_exr: channel count must be 1, 3 or 4");
+    return write_channels("write_exr", path, data, w, h, c, rgb_names(c));
+}
+
+/* Reads files produced by amvpt_host_write_exr (same layout). */
+extern "C" int amvpt_host_read_exr(const char *path, float *data, uint32_t w, uint32_t h, uint32_t c) {
+    if (c != 1 && c != 3 && c != 4) return fail("read_exr: channel count must be 1, 3 or 4");
+    return read_channels("read_exr", path, data, w, h, c, rgb_names(c));
+}
+
+extern "C" int amvpt_host_write_exr_channels(const char *path, const float *data, uint32_t w, uint32_t h, uint32_t c,
+                                             const char *const *names) {
+    return write_channels("write_exr_channels", path, data, w, h, c, names);
+}
+
+extern "C" int amvpt_host_read_exr_channels(const char *path, float *data, uint32_t w, uint32_t h, uint32_t c,
+                                            const char *const *names) {
+    return read_channels("read_exr_channels", path, data, w, h, c, names);
 }

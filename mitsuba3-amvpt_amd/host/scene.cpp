@@ -945,10 +945,8 @@ static void ensure_buffer_u8(uint8_t *&buf, size_t &have, size_t bytes, uint64_t
     buf = static_cast<uint8_t *>(grown(old, have, bytes, allocs, what));
 }
 
-/* One frame into the scene's cached ImageBlock on the current device, enqueued on `stream` (render_mu held):
- * the device scene and the film are created on first use and kept. */
-static amvpt_host_scene::DeviceCache *render_cached(amvpt_host_scene *s, const mi::SensorInfo &sn, const amvpt_params &p,
-                                                    void *stream, amvpt_counters *counters) {
+/* the scene's cache slot of the current device with its device scene, created on first use and kept (render_mu held) */
+static amvpt_host_scene::DeviceCache *device_cache(amvpt_host_scene *s) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) dev = 0;
     amvpt_host_scene::DeviceCache *dc = nullptr;
@@ -963,6 +961,14 @@ static amvpt_host_scene::DeviceCache *render_cached(amvpt_host_scene *s, const m
         if (amvpt_scene_create(&s->desc, &dc->scene) != AMVPT_OK) throw std::runtime_error(amvpt_last_error());
         ++s->scene_creates;
     }
+    return dc;
+}
+
+/* One frame into the scene's cached ImageBlock on the current device, enqueued on `stream` (render_mu held):
+ * the device scene and the film are created on first use and kept. */
+static amvpt_host_scene::DeviceCache *render_cached(amvpt_host_scene *s, const mi::SensorInfo &sn, const amvpt_params &p,
+                                                    void *stream, amvpt_counters *counters) {
+    amvpt_host_scene::DeviceCache *dc = device_cache(s);
     const hipStream_t st = (hipStream_t) stream;
     const uint32_t C = amvpt_film_channels(&p);
     const size_t npx = (size_t) p.film_width * p.film_height;
@@ -1051,6 +1057,36 @@ int amvpt_host_render_stream(amvpt_host_scene *s, uint32_t si, uint32_t seed, ui
         if (hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, st) != hipSuccess ||
             hipStreamSynchronize(st) != hipSuccess)
             throw std::runtime_error("copying the image to the host failed");
+        return 0;
+    });
+}
+
+/* guide records and planar depth of the whole quilt crop, on the cached device scene and buffers of their own */
+int amvpt_host_guides(amvpt_host_scene *s, uint32_t si, float *guides_out, float *depth_out) {
+    return guarded([&] {
+        if (!s || si >= s->sensors.size()) throw std::runtime_error("Scene::render(): sensor index out of bounds!");
+        const mi::SensorInfo &sn = s->sensors[si];
+        const amvpt_params p = mi::params_for(*s, sn, 0, 0);
+        std::lock_guard<std::mutex> lock(s->render_mu);
+        amvpt_host_scene::DeviceCache *dc = device_cache(s);
+        const size_t npx = (size_t) p.film_width * p.film_height;
+        struct Buf {
+            float *p = nullptr;
+            ~Buf() { if (p) (void) hipFree(p); }
+        } g, z;
+        if (hipMalloc(&g.p, npx * 8 * sizeof(float)) != hipSuccess) throw std::runtime_error("hipMalloc of the guide records failed");
+        if (amvpt_guides(dc->scene, sn.views.data(), &p, nullptr, g.p, nullptr) != AMVPT_OK)
+            throw std::runtime_error(amvpt_last_error());
+        if (depth_out) {
+            if (hipMalloc(&z.p, npx * sizeof(float)) != hipSuccess) throw std::runtime_error("hipMalloc of the depth plane failed");
+            if (amvpt_guide_depth(g.p, sn.views.data(), p.n_views, npx, z.p, nullptr) != AMVPT_OK)
+                throw std::runtime_error(amvpt_last_error());
+            if (hipMemcpy(depth_out, z.p, npx * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+                throw std::runtime_error("copying the depth plane to the host failed");
+        }
+        if (guides_out && hipMemcpy(guides_out, g.p, npx * 8 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+            throw std::runtime_error("copying the guide records to the host failed");
+        if (hipStreamSynchronize(nullptr) != hipSuccess) throw std::runtime_error("amvpt_host_guides: the device reported an error");
         return 0;
     });
 }

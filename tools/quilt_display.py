@@ -2,11 +2,12 @@
 """Renders a scene to the 8-bit quilt PNG and the interlaced PNG of a lenticular display.
 
     python tools/quilt_display.py [scene.xml] [-D key=value ...] [--preset NAME --presets presets.csv]
-                                  [--size W H] [--nearest] [--out-dir DIR]
+                                  [--size W H] [--nearest] [--out-dir DIR] [--depth PATH]
 
 Without arguments: scenes/cbox_grid.xml at a small resolution, the default preset (LKG4x8) with the scene's view
 grid, a 1280 x 720 display, written to out/<scene>_quilt.png and out/<scene>_display.png.  The frame is rendered once;
-both images come from that frame.
+both images come from that frame.  --depth PATH also writes the depth quilt (nearer brighter, background black, scaled to
+the frame's own depth range) as an 8-bit PNG: the RGB-D companion of the quilt.
 """
 import argparse
 import os
@@ -27,6 +28,7 @@ def main():
     ap.add_argument("--spp", type=int, default=0)
     ap.add_argument("--nearest", action="store_true")
     ap.add_argument("--out-dir", default=os.path.join(REPO, "out"))
+    ap.add_argument("--depth", metavar="PATH", help="also write the depth quilt (amvpt.display.depth_quilt) as a PNG")
     a = ap.parse_args()
 
     import amvpt
@@ -54,6 +56,8 @@ def main():
     stem = os.path.join(a.out_dir, os.path.splitext(os.path.basename(a.scene))[0])
     D.write_png(stem + "_quilt.png", quilt)
     D.write_png(stem + "_display.png", image)
+    if a.depth:
+        D.write_png(a.depth, D.depth_quilt(scene))
     used = preset if preset is not None else D.preset_for_scene(scene)
     print("%s: quilt %d x %d -> %s_quilt.png, display %d x %d (%s, grid %d x %d) -> %s_display.png, %d lanes" % (
         os.path.basename(a.scene), w, h, stem, a.size[0], a.size[1], used.name, used.grid[0], used.grid[1], stem,
