@@ -12,6 +12,7 @@
  *   amvpt_host_write_exr                 <- Film::write (hdrfilm.cpp, OpenEXR float32)
  *   amvpt_host_guides                    <- the aov integrator's position / geo_normal / shape_index
  *                                           (src/integrators/aov.cpp:245-300; see amvpt_guides.h)
+ *   amvpt_host_denoise_stream            <- nothing: the reference has no denoiser (see amvpt_denoise.h)
  *   amvpt_host_display / _write_png     <- Program::display_image(screenshot) + Bitmap::write
  *                                           (src/mitsuba/program.cpp:199-276)
  *   amvpt_host_read_presets / _write_presets <- Preset::import_file / export_file (src/mitsuba/preset.h)
@@ -27,6 +28,7 @@
 #include "amvpt.h"
 #include "amvpt_display.h"
 #include "amvpt_guides.h"
+#include "amvpt_denoise.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -171,6 +173,21 @@ int amvpt_host_display_stream(amvpt_host_scene *scene, uint32_t sensor_index, ui
 int amvpt_host_redisplay_stream(amvpt_host_scene *scene, uint32_t sensor_index, const amvpt_display_preset *preset,
                                 int quilt, int nearest, uint32_t dst_w, uint32_t dst_h, uint8_t *out_host_u8,
                                 void *stream);
+
+/*
+ * The denoiser (amvpt_denoise.h) on the current device and a caller stream (hipStream_t; NULL: the default stream).
+ * image_host NULL: the input is the developed frame that the last amvpt_host_render* (raw == 0) or
+ * amvpt_host_display* of this sensor left on the device (an error when none is cached); otherwise image_host
+ * (height x width x developed channels float32, amvpt_host_film_info's) is uploaded and filtered.  The guide
+ * records come from amvpt_guides on the device scene amvpt_host_render caches (created on first use: a call after a
+ * render creates no second one, see amvpt_host_render_stats).  params is required; sigma_plane is in world units.
+ * out_host (NULL: nothing is downloaded) receives the filtered image.  replace != 0: the filtered image also becomes
+ * the cached developed frame, so that amvpt_host_redisplay_stream shows it.  The cached film is not touched.
+ * amvpt_host_render_multi has no denoise path; a view-group rank may run amvpt_denoise over the rectangle of its own
+ * whole tiles and gets this entry's result there, because no tap crosses a view.
+ */
+int amvpt_host_denoise_stream(amvpt_host_scene *scene, uint32_t sensor_index, const amvpt_denoise_params *params,
+                              const float *image_host, int replace, float *out_host, void *stream);
 
 /* The default preset (LKG4x8) with `grid` set from the sensor's grid_x / grid_y; a batch sensor gives n x 1. */
 int amvpt_host_preset_for_scene(amvpt_host_scene *scene, uint32_t sensor_index, amvpt_display_preset *preset);

@@ -112,6 +112,23 @@ class FixedWindow(ctypes.Structure):
                 ("overflow", ctypes.c_void_p), ("overflow_capacity", u64)]
 
 
+class DenoiseParams(ctypes.Structure):
+    """amvpt_denoise_params (include/amvpt_denoise.h).  Without arguments: amvpt_denoise_default_params' values,
+    {3, 1.0, 0.01, 0.05, 5}; sigma_plane is in world units."""
+    _fields_ = [("iterations", u32), ("sigma_color", f32), ("color_floor", f32), ("sigma_plane", f32),
+                ("normal_squarings", u32)]
+
+    def __init__(self, iterations=3, sigma_color=1.0, color_floor=0.01, sigma_plane=0.05, normal_squarings=5):
+        super().__init__(iterations, sigma_color, color_floor, sigma_plane, normal_squarings)
+
+    def values(self):
+        return (self.iterations, self.sigma_color, self.color_floor, self.sigma_plane, self.normal_squarings)
+
+    def __repr__(self):
+        return ("DenoiseParams(iterations=%r, sigma_color=%r, color_floor=%r, sigma_plane=%r, normal_squarings=%r)"
+                % self.values())
+
+
 # amvpt_run_exchange_fn: (ctx, n_runs, *run_lane_begin, *run_count, *run_prefix, *total) -> 0 on success
 RunExchangeFn = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, u32, ctypes.POINTER(u64), ctypes.POINTER(u64),
                                  ctypes.POINTER(u64), ctypes.POINTER(u64))
@@ -234,8 +251,63 @@ def hip_lib():
                              ("amvpt_depth8_host", [vp, u32, u32, f32, f32, vp])):
                 getattr(L, fn).restype = ctypes.c_int
                 getattr(L, fn).argtypes = args
+        if hasattr(L, "amvpt_denoise_version"):   # include/amvpt_denoise.h
+            vp = ctypes.c_void_p
+            L.amvpt_denoise_version.restype = u32
+            L.amvpt_denoise_default_params.restype = DenoiseParams
+            L.amvpt_denoise_default_params.argtypes = []
+            L.amvpt_denoise.restype = L.amvpt_denoise_host.restype = ctypes.c_int
+            L.amvpt_denoise.argtypes = [vp, u32, u32, u32, vp, ctypes.POINTER(DenoiseParams), vp, vp, vp]
+            L.amvpt_denoise_host.argtypes = [vp, u32, u32, u32, vp, ctypes.POINTER(DenoiseParams), vp, vp]
         _hip = L
     return _hip
+
+
+def denoise_version():
+    """AMVPT_DENOISE_VERSION of the loaded library (include/amvpt_denoise.h)."""
+    return hip_lib().amvpt_denoise_version()
+
+
+def denoise_default_params():
+    """amvpt_denoise_default_params of the loaded library."""
+    c = hip_lib().amvpt_denoise_default_params()
+    return DenoiseParams(*c.values())
+
+
+def denoise_device(image_ptr, channels, width, height, guides_ptr, out_ptr, scratch_ptr=None, params=None, stream=None):
+    """amvpt_denoise over device pointers, ordered on `stream`: the height x width x channels float32 image and its
+    height x width x 8 guide records -> out_ptr; scratch_ptr (the image's size) may be None when iterations is 1."""
+    L = hip_lib()
+    q = params if params is not None else denoise_default_params()
+    _check(L.amvpt_denoise(ctypes.c_void_p(image_ptr), channels, width, height, ctypes.c_void_p(guides_ptr),
+                           ctypes.byref(q), ctypes.c_void_p(out_ptr), ctypes.c_void_p(scratch_ptr or 0),
+                           ctypes.c_void_p(stream or 0)), L)
+
+
+def denoise_host(image, guides, params=None):
+    """amvpt_denoise_host over numpy: (H, W, 3 or 4) float32 image and (H, W, 8) guide records -> the filtered image.
+    Bit-identical to the device entry; needs no device."""
+    L = hip_lib()
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    g = np.ascontiguousarray(guides, dtype=np.float32)
+    if img.ndim != 3 or g.shape != img.shape[:2] + (8,):
+        raise ValueError("denoise_host: an (H, W, C) image and (H, W, 8) guide records of its size are needed")
+    q = params if params is not None else denoise_default_params()
+    h, w, c = img.shape
+    out = np.empty_like(img)
+    scratch = np.empty_like(img) if q.iterations > 1 else None
+    _check(L.amvpt_denoise_host(img.ctypes.data, c, w, h, g.ctypes.data, ctypes.byref(q), out.ctypes.data,
+                                scratch.ctypes.data if scratch is not None else None), L)
+    return out
+
+
+def denoise_sigma_plane(guides):
+    """The default sigma_plane of `denoise` for these guide records: 1/40 of the largest side of the bounding box
+    of their hit points, as a float32 (0.05 for the Cornell box; the C default when nothing is hit)."""
+    g = np.asarray(guides, dtype=np.float32).reshape(-1, 8)
+    pts = g[g[:, 0] >= 0][:, 4:7]
+    side = np.float32((pts.max(axis=0) - pts.min(axis=0)).max()) if len(pts) else np.float32(0)
+    return float(side / np.float32(40)) if side > 0 else 0.05
 
 
 def guides_version():
@@ -395,6 +467,9 @@ def host_lib():
             names = ctypes.POINTER(ctypes.c_char_p)
             L.amvpt_host_write_exr_channels.argtypes = [ctypes.c_char_p, ctypes.c_void_p, u32, u32, u32, names]
             L.amvpt_host_read_exr_channels.argtypes = [ctypes.c_char_p, ctypes.c_void_p, u32, u32, u32, names]
+        if hasattr(L, "amvpt_host_denoise_stream"):
+            L.amvpt_host_denoise_stream.argtypes = [ctypes.c_void_p, u32, ctypes.POINTER(DenoiseParams), ctypes.c_void_p,
+                                                    ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
         L.amvpt_host_parse_fov.argtypes = [f64, ctypes.c_char_p, ctypes.c_char_p, f64]
         L.amvpt_host_parse_fov.restype = f64
         L.amvpt_host_perspective_projection.argtypes = [ctypes.POINTER(ctypes.c_int)] * 3 + [f32, f32, f32,
@@ -681,6 +756,48 @@ def depth(scene, sensor=0):
     """Planar depth of every quilt pixel -> (H, W) float32: the camera-space z of the primary hit in the pixel's
     own view, +inf on a miss (amvpt_host_guides)."""
     return _host_guides(scene, sensor, False, True)[1]
+
+
+def denoise_params_for(scene, sensor=0, params=None, **fields):
+    """The DenoiseParams `denoise` uses: `params` as given, or the defaults with the given fields replaced and, where
+    sigma_plane is not among them, denoise_sigma_plane of the scene's guide records."""
+    if params is not None:
+        if fields:
+            raise ValueError("denoise: give either params or single fields, not both")
+        return params
+    q = DenoiseParams(**fields)
+    if "sigma_plane" not in fields:
+        q.sigma_plane = denoise_sigma_plane(guides(scene, sensor))
+    return q
+
+
+def host_denoise(scene, params, image=None, sensor=0, replace=False, download=True, stream=None):
+    """amvpt_host_denoise_stream: amvpt_denoise on the device over `image` (None: the developed frame the last render
+    or display of this sensor cached there) and the guide records of the cached device scene -> the filtered image
+    (None with download=False).  replace=True makes it the cached frame, which display(rerender=False) then shows."""
+    w, h, c, _ = scene.film_info(sensor)
+    img = None
+    if image is not None:
+        img = np.ascontiguousarray(image, dtype=np.float32)
+        if img.shape != (h, w, c):
+            raise ValueError("denoise: the image must be (%d, %d, %d), the sensor's developed frame" % (h, w, c))
+    out = np.zeros((h, w, c), dtype=np.float32) if download else None
+    _check(scene._lib.amvpt_host_denoise_stream(scene._h, sensor, ctypes.byref(params),
+                                                img.ctypes.data if img is not None else None, int(bool(replace)),
+                                                out.ctypes.data if out is not None else None,
+                                                ctypes.c_void_p(stream or 0)), scene._lib)
+    return out
+
+
+def denoise(scene, image=None, sensor=0, seed=0, spp=0, params=None, stream=None, **fields):
+    """The a-trous denoiser (include/amvpt_denoise.h) on the device: `image` (None: a fresh render of `sensor` with
+    `seed` and `spp`, developed) filtered with the scene's guide records -> (H, W, C) float32.  `params` is a
+    DenoiseParams; otherwise its fields are keywords (iterations, sigma_color, color_floor, sigma_plane,
+    normal_squarings) over the defaults, with sigma_plane from denoise_sigma_plane of the scene."""
+    q = denoise_params_for(scene, sensor, params, **fields)
+    if image is None:
+        render(scene, sensor=sensor, seed=seed, spp=spp, stream=stream)
+    return host_denoise(scene, q, image=image, sensor=sensor, stream=stream)
 
 
 GUIDE_CHANNELS = ("Z", "N.X", "N.Y", "N.Z", "P.X", "P.Y", "P.Z", "id", "view")

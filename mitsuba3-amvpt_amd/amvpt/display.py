@@ -163,12 +163,21 @@ def preset_for_scene(scene, sensor=0):
 
 
 def display(scene, preset=None, size=(1280, 720), quilt=False, nearest=False, sensor=0, seed=0, spp=0,
-            counters=None, stream=None, rerender=True):
+            counters=None, stream=None, rerender=True, denoise=None):
     """Render `scene` and run the display stage on the device (amvpt_host_display): render -> develop -> sRGB
     quilt -> lenticular image, one download -> (size[1], size[0], 3) uint8.  preset None: preset_for_scene.
     rerender=False runs the stage alone on the developed frame the last render / display of this sensor left on
-    the device (amvpt_host_redisplay_stream): another preset, size or mode for the same frame."""
+    the device (amvpt_host_redisplay_stream): another preset, size or mode for the same frame.
+    denoise None: the frame as rendered.  An amvpt.DenoiseParams, or True for amvpt.denoise's defaults, filters the
+    developed frame on the device between develop and the sRGB quilt (amvpt_host_denoise_stream); the filtered frame
+    is the cached one afterwards, so with rerender=False a frame already filtered is filtered again."""
     _, H = _libs()
+    if denoise is not None and denoise is not False:
+        if rerender:
+            amvpt.render(scene, sensor=sensor, seed=seed, spp=spp, counters=counters, stream=stream)
+        q = amvpt.denoise_params_for(scene, sensor, denoise if isinstance(denoise, amvpt.DenoiseParams) else None)
+        amvpt.host_denoise(scene, q, sensor=sensor, replace=True, download=False, stream=stream)
+        rerender = False
     w, h = int(size[0]), int(size[1])
     out = np.zeros((max(h, 0), max(w, 0), 3), dtype=np.uint8)
     if not rerender:

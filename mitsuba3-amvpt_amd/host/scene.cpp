@@ -1145,6 +1145,51 @@ int amvpt_host_redisplay_stream(amvpt_host_scene *s, uint32_t si, const amvpt_di
     });
 }
 
+/* amvpt_denoise over the cached developed frame (or an uploaded image) and the guide records of the cached device scene */
+int amvpt_host_denoise_stream(amvpt_host_scene *s, uint32_t si, const amvpt_denoise_params *params, const float *image_host,
+                              int replace, float *out, void *stream) {
+    return guarded([&] {
+        if (!s || si >= s->sensors.size()) throw std::runtime_error("Scene::render(): sensor index out of bounds!");
+        if (!params) throw std::runtime_error("amvpt_host_denoise: null params");
+        const mi::SensorInfo &sn = s->sensors[si];
+        const amvpt_params p = mi::params_for(*s, sn, 0, 0);
+        const uint32_t T = p.film_alpha ? 4u : 3u;
+        const size_t npx = (size_t) p.film_width * p.film_height, bytes = npx * T * sizeof(float);
+        const hipStream_t st = (hipStream_t) stream;
+        std::lock_guard<std::mutex> lock(s->render_mu);
+        amvpt_host_scene::DeviceCache *dc = device_cache(s);
+        if (!image_host && (!dc->image_w || dc->image_sensor != si || dc->image_w != p.film_width ||
+                            dc->image_h != p.film_height || dc->image_ch != T))
+            throw std::runtime_error("amvpt_host_denoise: no developed frame of this sensor is cached on the current device "
+                                     "(render or display it first, or pass an image)");
+        /* buffers of the call's own, freed once the stream has drained */
+        struct Buf {
+            float *p = nullptr;
+            hipStream_t st;
+            ~Buf() { if (p) { (void) hipStreamSynchronize(st); (void) hipFree(p); } }
+        } g{nullptr, st}, up{nullptr, st}, a{nullptr, st}, b{nullptr, st};
+        if (hipMalloc(&g.p, npx * 8 * sizeof(float)) != hipSuccess || hipMalloc(&a.p, bytes) != hipSuccess ||
+            (params->iterations > 1u && hipMalloc(&b.p, bytes) != hipSuccess) ||
+            (image_host && hipMalloc(&up.p, bytes) != hipSuccess))
+            throw std::runtime_error("hipMalloc of the denoiser's buffers failed");
+        if (image_host && hipMemcpyAsync(up.p, image_host, bytes, hipMemcpyHostToDevice, st) != hipSuccess)
+            throw std::runtime_error("copying the image to the device failed");
+        if (amvpt_guides(dc->scene, sn.views.data(), &p, nullptr, g.p, stream) != AMVPT_OK ||
+            amvpt_denoise(image_host ? up.p : dc->image, T, p.film_width, p.film_height, g.p, params, a.p, b.p, stream) != AMVPT_OK)
+            throw std::runtime_error(amvpt_last_error());
+        if (replace) {
+            ensure_buffer(dc->image, dc->image_bytes, bytes, s->buffer_allocs);
+            if (hipMemcpyAsync(dc->image, a.p, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess)
+                throw std::runtime_error("copying the filtered frame into the cache failed");
+            dc->image_w = p.film_width, dc->image_h = p.film_height, dc->image_ch = T, dc->image_sensor = si;
+        }
+        if (out && hipMemcpyAsync(out, a.p, bytes, hipMemcpyDeviceToHost, st) != hipSuccess)
+            throw std::runtime_error("copying the filtered image to the host failed");
+        if (hipStreamSynchronize(st) != hipSuccess) throw std::runtime_error("amvpt_host_denoise: the device reported an error");
+        return 0;
+    });
+}
+
 int amvpt_host_display(amvpt_host_scene *s, uint32_t si, uint32_t seed, uint32_t spp, const amvpt_display_preset *preset,
                        int quilt, int nearest, uint32_t dst_w, uint32_t dst_h, uint8_t *out, amvpt_counters *counters) {
     return amvpt_host_display_stream(s, si, seed, spp, preset, quilt, nearest, dst_w, dst_h, out, nullptr, counters);

@@ -3,11 +3,13 @@
 
     python tools/quilt_display.py [scene.xml] [-D key=value ...] [--preset NAME --presets presets.csv]
                                   [--size W H] [--nearest] [--out-dir DIR] [--depth PATH]
+                                  [--denoise [ITER]]
 
 Without arguments: scenes/cbox_grid.xml at a small resolution, the default preset (LKG4x8) with the scene's view
 grid, a 1280 x 720 display, written to out/<scene>_quilt.png and out/<scene>_display.png.  The frame is rendered once;
 both images come from that frame.  --depth PATH also writes the depth quilt (nearer brighter, background black, scaled to
-the frame's own depth range) as an 8-bit PNG: the RGB-D companion of the quilt.
+the frame's own depth range) as an 8-bit PNG: the RGB-D companion of the quilt.  --denoise [ITER] filters the developed
+frame on the device before both images are made (amvpt.denoise's defaults; ITER iterations instead of 3).
 """
 import argparse
 import os
@@ -29,6 +31,8 @@ def main():
     ap.add_argument("--nearest", action="store_true")
     ap.add_argument("--out-dir", default=os.path.join(REPO, "out"))
     ap.add_argument("--depth", metavar="PATH", help="also write the depth quilt (amvpt.display.depth_quilt) as a PNG")
+    ap.add_argument("--denoise", type=int, nargs="?", const=3, default=None, metavar="ITER",
+                    help="filter the frame with the a-trous denoiser (amvpt.denoise), ITER iterations (default 3)")
     a = ap.parse_args()
 
     import amvpt
@@ -50,7 +54,11 @@ def main():
     cnt = amvpt.Counters()
     # one render; the 8-bit quilt from its download (the host entry gives the device's bytes), the display image
     # from the stage run on the frame the render left on the device
-    quilt = D.srgb8(amvpt.render(scene, seed=a.seed, spp=a.spp, counters=cnt))
+    frame = amvpt.render(scene, seed=a.seed, spp=a.spp, counters=cnt)
+    if a.denoise is not None:   # the filtered frame replaces the cached one: the display image below shows it
+        q = amvpt.denoise_params_for(scene, iterations=a.denoise)
+        frame = amvpt.host_denoise(scene, q, replace=True)
+    quilt = D.srgb8(frame)
     image = D.display(scene, preset, size=tuple(a.size), nearest=a.nearest, rerender=False)
     os.makedirs(a.out_dir, exist_ok=True)
     stem = os.path.join(a.out_dir, os.path.splitext(os.path.basename(a.scene))[0])
