@@ -419,6 +419,9 @@ enum {
     AMVPT_OPT_BLOCK_SPLAT = 512u,     /* ABI 12: the splat takes the per-lane block window even where the row-reduced
                                        * splat is eligible (every filter, the default Gaussian included); results are
                                        * identical up to float summation order */
+    AMVPT_OPT_GENERIC_FLUSH = 2048u,  /* the row splat's wave windows keep the run-time geometry and the generic
+                                       * flush loop everywhere (no fixed-pitch window, no static flush); results are
+                                       * identical up to float summation order.  A flag bit only: ABI 12 */
     AMVPT_OPT_DETERMINISTIC = 16u     /* bitwise-reproducible film: splats summed as 32.32 fixed point with
                                        * integer atomics (order-independent), added to the film once at the
                                        * end; each footprint-cell add is rounded to a multiple of 2^-32 and

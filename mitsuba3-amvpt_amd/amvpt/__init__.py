@@ -149,6 +149,7 @@ OPT_NO_BOX_SCREEN = 64
 OPT_THREADED_BVH = 128
 OPT_SPLIT_PRIMARY = 256
 OPT_BLOCK_SPLAT = 512   # ABI 12: the per-lane block-window splat even where the row-reduced one is eligible
+OPT_GENERIC_FLUSH = 2048  # the row splat's wave windows with run-time geometry and the generic flush loop everywhere
 OPT_FIXED_DIRECT = 1024  # amvpt_fixed.h: direct puts into the fixed-point film instead of the integer LDS window
 
 # amvpt_params.rfilter

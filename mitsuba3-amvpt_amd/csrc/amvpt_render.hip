@@ -261,6 +261,7 @@ struct KParams {
     float bin_lo[3], bin_scale[3];   /* ray binning: the scene box's low corner and cells per unit (bin_key) */
     uint32_t filt_kind;   /* FILT_* of `filt` (dmath.h): what the FK_ANY splat instances evaluate */
     uint32_t fx_direct;   /* film_fx set: direct puts (AMVPT_OPT_FIXED_DIRECT) instead of the integer LDS window */
+    uint32_t generic_flush;   /* AMVPT_OPT_GENERIC_FLUSH: wave windows keep the run-time geometry and wave_flush's loop */
 };
 
 /* the PCG32 a stock-path lane starts the pass with: TEA-seeded, or the previous pass's state (same
@@ -1292,7 +1293,9 @@ AD void row_put_win(const KParams &P, float *film, WinT *const wbase, const Win 
         for (int c = 0; c < 5; ++c) wx[c] = union_weight<kF>(F, f.rx, f.x0, ux0 + c, x0c, x1);
         wx[5] = 0.f;
         if (!u5) wx[5] = union_weight<kF>(F, f.rx, f.x0, ux0 + 5, x0c, x1);
-        WinT *const wch = wbase + ch * wn.plane;
+        /* the lane's first cell, union row 3 b2 and column 3 b3: its nine cells are r rows and c columns further on
+         * (one address per view; the row step is wave-uniform, the column an immediate offset) */
+        WinT *const cell0 = wbase + ch * wn.plane + (uy0 + 3 * b2 - wn.by0) * wn.rs + (ux0 + 3 * b3 - wn.bx0);
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
             /* row position r + 3 h holds union row r + 3 (h ^ b2); the quad shares b2 */
@@ -1334,7 +1337,7 @@ AD void row_put_win(const KParams &P, float *film, WinT *const wbase, const Win 
                 const float u = keep + dpp_f<DPP_ROR8>(send);
                 const int col = c + 3 * b3;
                 if (ux0 + col < ux1 && uy0 + row < uy1)
-                    win_add(wch + (uy0 + row - wn.by0) * wn.rs + (ux0 + col - wn.bx0), u);
+                    win_add(cell0 + r * wn.rs + c, u);
             }
         }
     } else if (act) {
@@ -1350,13 +1353,11 @@ AD void row_put_win(const KParams &P, float *film, WinT *const wbase, const Win 
  * cells per lane -- four LDS reads, one wait -- measured no faster and its live pointers pushed
  * the 5-wave register budget into scratch.) */
 template <int C, bool kWin = true>
-AD void wave_flush(const KParams &P, float *film, WinT *win, const Win &w) {
+AD void wave_flush(const KParams &P, float *film, WinT *win, const Win &w, bool inside) {
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     const int rowlen = w.ww * C;
     const int n_elems = rowlen * w.wh;
     const float inv_rowlen = 1.f / (float) max(rowlen, 1);
-    /* the wave window's quilt cells inside the film window (uniform; always for the whole quilt) */
-    const bool inside = in_window<kWin>(P, w.bx0, w.by0) && in_window<kWin>(P, w.bx0 + w.ww - 1, w.by0 + w.wh - 1);
     float *film0 = inside ? film_cell<kWin>(P, film, w.bx0, w.by0, 0) : film;
     const uint32_t film_row = (kWin ? P.fw : P.W) * (uint32_t) C;
     for (int e = (int) __lane_id(); e < n_elems; e += 64) {
@@ -1372,6 +1373,41 @@ AD void wave_flush(const KParams &P, float *film, WinT *win, const Win &w) {
             if (v != 0.f || v != v) {
                 if (inside) atomicAdd(film0 + ((uint32_t) cy * film_row + (uint32_t) r), v);   /* never deterministic */
                 else film_cell_add<kWin, false>(P, film, w.bx0 + cx, w.by0 + cy, k, v);
+            }
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+}
+/* The fixed-pitch wave window (wave_put, boxes of at most kFixW columns): rows kFixW cells apart, planes kFixPlane
+ * apart -- what the run-time geometry gives a 5- or 6-row window of that width (rows 16 mod 32 apart, planes 4 mod
+ * 32 apart: row_put's bank spread, see window_bbox); 6 rows end at cell 5 * 16 + 15 < 100, so the layout holds every
+ * height. */
+constexpr int kFixW = 16, kFixPlane = 100;
+static_assert(kFixW * kWaveWinH <= kFixPlane && kFixPlane <= kWavePlane, "fixed-pitch wave window");
+/* wave_flush of a fixed-pitch RGBW window that lies inside the film window: the lane's cell is fixed for the whole
+ * kernel (channel lane & 3 of column lane >> 2), a window row is 64 consecutive film floats, and the rows' reads are
+ * issued together and waited for once.  All kWaveWinH rows are read: the adds stay inside the window's ww x wh cells,
+ * so every other cell is zero and is skipped as wave_flush skips an untouched one.  The same cells are flushed and
+ * re-zeroed, with the same conversions and tests, one atomic per touched film float.  (Six f64 cells in flight stay
+ * inside the 5-wave register budget: the row block above, not the flush, sets the kernel's allocation.) */
+template <bool kWin = true>
+AD void wave_flush_fixed(const KParams &P, float *film, WinT *win, const Win &w) {
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    const uint32_t lane = __lane_id();
+    float *const film0 = film_cell<kWin>(P, film, w.bx0, w.by0, 0);
+    const uint32_t film_row = (kWin ? P.fw : P.W) * 4u;
+    if ((int) (lane >> 2) < w.ww) {
+        WinT *const src = win + (lane & 3u) * kFixPlane + (lane >> 2);
+        WinT d[kWaveWinH];
+#pragma unroll
+        for (int it = 0; it < kWaveWinH; ++it) d[it] = src[it * kFixW];
+#pragma unroll
+        for (int it = 0; it < kWaveWinH; ++it) {
+            if (__double_as_longlong(d[it]) != 0ll) {
+                src[it * kFixW] = 0.0;
+                const float v = (float) d[it];
+                float *const frow = film0 + (size_t) ((uint32_t) it * film_row);   /* uniform: a scalar base */
+                if (v != 0.f || v != v) atomicAdd(frow + lane, v);   /* never deterministic */
             }
         }
     }
@@ -1403,20 +1439,28 @@ AD void wave_put(const KParams &P, float *film, WaveLds<C> &L, float px, float p
     wn.bx0 = bx0; wn.by0 = by0;
     wn.ww = min(bx1 - bx0, kWaveWinW);
     wn.wh = min(by1 - by0, kWaveWinH);
+    WinT *const win = L.win + (threadIdx.x >> 6) * (kWavePlane * C);
+    /* the wave window's quilt cells inside the film window (uniform; always for the whole quilt) */
+    const bool inside = in_window<kWin>(P, wn.bx0, wn.by0) && in_window<kWin>(P, wn.bx0 + wn.ww - 1, wn.by0 + wn.wh - 1);
+    /* the common box (uniform): the fixed-pitch window, and its static flush when it lies inside the film window */
+    const bool fixed = C == 4 && wn.ww <= kFixW && !P.generic_flush;
     wn.rs = wn.ww;
     wn.plane = wn.ww * wn.wh;
     /* row_put's bank spread (see window_bbox): rows 16 mod 32 apart, planes 4 mod 32 apart */
-    {
+    if (fixed) {
+        wn.rs = kFixW;
+        wn.plane = kFixPlane;
+    } else {
         const int r2 = (wn.ww & ~31) + 16, r3 = r2 >= wn.ww ? r2 : r2 + 32;
         if (r3 * wn.wh + 32 <= kWavePlane) wn.rs = r3;
         wn.plane = wn.rs * wn.wh;
         wn.plane += (36 - (wn.plane & 31)) & 31;
         if (wn.plane > kWavePlane) { wn.rs = wn.ww; wn.plane = wn.ww * wn.wh; }
     }
-    WinT *const win = L.win + (threadIdx.x >> 6) * (kWavePlane * C);
     /* row_put reads the window through L.win: hand it this wave's window */
     row_put_win<C, kWin, kF>(P, film, win, wn, f, act, vals, coalesce, fallback, ub);
-    wave_flush<C, kWin>(P, film, win, wn);
+    if (fixed && inside) wave_flush_fixed<kWin>(P, film, win, wn);
+    else wave_flush<C, kWin>(P, film, win, wn, inside);
 }
 
 /*
@@ -4276,6 +4320,7 @@ static void plan_params(const RenderCall &c, RenderPlan &pl) {
     P.trav_mode = c.opts.traversal;
     P.box_screen = (c.opts.flags & AMVPT_OPT_NO_BOX_SCREEN) ? 0u : 1u;
     P.split_prim = (c.opts.flags & AMVPT_OPT_SPLIT_PRIMARY) ? 1u : 0u;
+    P.generic_flush = (c.opts.flags & AMVPT_OPT_GENERIC_FLUSH) ? 1u : 0u;
     for (int a = 0; a < 3; ++a) {
         const float ext = scene->root_hi[a] - scene->root_lo[a];
         P.bin_lo[a] = scene->root_lo[a];
