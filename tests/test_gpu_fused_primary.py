@@ -66,6 +66,10 @@ CASES = {
     "thinlens": (dict(res=24, spp=16, gx=4, gy=2, reuse=8, cam="thinlens", aperture="0.05"), dict()),
     # no walk at all / no suffix push
     "depth0": (dict(res=32, spp=16, max_depth=0), dict()),
+    # max_depth 1 is not "emission only" in mvpath: the primary vertex's emitter sample is added whatever the depth
+    # limit (mvpath_multi.h:248-267; :531 gates the suffix alone), while the fill's sample_single honours it.  A
+    # uniform enclosure reads Le (1 + c rho / (n_adapt + 1)) with c ~ 0.34, not Le: a property of the reference,
+    # which is why tests/radiometry.py has no closed form for this depth
     "depth1": (dict(res=32, spp=16, max_depth=1), dict()),
     # a lane range with neither end on a wave boundary
     "lane_range": (dict(res=48, spp=16), dict(lane_begin=1003, lane_end=20021)),
