@@ -809,7 +809,9 @@ template <bool kSph> AD void brute_test(const DPrim &p, uint32_t pi, const Ray &
  *     hit on it is farther.
  * A grazing face is always tested (first).  Lanes take their
  * candidate faces in ascending crossing order, one face (two per-lane triangle loads) per round, so a lane
- * that hits its entry face is done after one round; the wave runs until its last lane is.
+ * that hits its entry face is done after one round; the wave runs until its last lane is.  The rounds are
+ * pooled over two boxes at a time (box_rounds): suffix rays are incoherent, so with a loop per box nearly every
+ * wave paid a round in each box for lanes that need less than half a round in all.
  */
 constexpr float kBoxEps = 1e-3f, kBoxEpsT = 1e-3f, kBoxGraze = 1e-3f;
 AD void box_candidates(const DBox &B, const Ray &r, float maxt, float *key, uint32_t &cand) {
@@ -867,49 +869,73 @@ template <class F> AD void loose_scan(const SceneRef &sc, uint32_t j0, uint32_t 
         b = load_uniform(sc.loose_prims, min(j + 3u, last));
     }
 }
-/* kAny: any hit in [0, ray.maxt] (found); else the closest hit (best, best_orig) */
-template <bool kAny>
-AD void box_walk(const SceneRef &sc, const Ray &ray, Hit &best, uint32_t &best_orig, bool &found) {
-    const uint32_t nb = ufirst(sc.n_boxes);
-    for (uint32_t bi = 0; bi < nb; ++bi) {
-        const DBox B = load_uniform(sc.boxes, bi);
-        float key[6];
-        uint32_t cand;
-        box_candidates(B, ray, ray.maxt, key, cand);
-        if (kAny && found) cand = 0u;
-        const DPrim *const bt = sc.box_prims + 12u * bi;
-        for (;;) {
-            /* the lane's next face: the candidate with the smallest crossing */
-            uint32_t k = 0u;
+/* The face rounds of kN (1 or 2) boxes from b0 on, pooled: the candidates of all kN boxes first (the box records
+ * stay uniform scalar loads), then one round loop in which a lane's next face is the candidate with the smallest
+ * key over all its boxes -- face f of box b0 + b is bit 6 b + f of `cand`, its triangles bt[2 (6 b + f) + j].
+ * Every round clears one candidate of each lane that takes part and a lane has at most 6 kN, so 6 kN rounds
+ * always suffice: the trip count is bounded at compile time. */
+template <bool kAny, int kN>
+AD void box_rounds(const SceneRef &sc, uint32_t b0, const Ray &ray, Hit &best, uint32_t &best_orig, bool &found) {
+    float key[6 * kN];
+    uint32_t cand = 0u;
+#pragma unroll
+    for (int b = 0; b < kN; ++b) {
+        const DBox B = load_uniform(sc.boxes, b0 + (uint32_t) b);
+        uint32_t c;
+        box_candidates(B, ray, ray.maxt, key + 6 * b, c);
+        cand |= c << (6 * b);
+    }
+    if (kAny && found) cand = 0u;
+    const DPrim *const bt = sc.box_prims + 12u * b0;
+#pragma nounroll
+    for (int round = 0; round < 6 * kN; ++round) {
+        uint32_t k = 0u;
+        bool act = cand != 0u;
+        if constexpr (kAny) {
+            /* any hit: a disjunction over the candidates, and with no best hit there is nothing to cull by, so
+             * the order only decides how soon a lane is done -- and nearly every candidate of a shadow segment
+             * is a face the segment really crosses, a hit whichever comes first.  The lane's lowest candidate
+             * bit (one instruction) instead of the pick over 6 kN keys; the keys are dead in this walk. */
+            k = (uint32_t) __ffs((int) cand) - 1u;   /* cand = 0: no face, and act is false */
+        } else {
+            /* the lane's next face: the candidate with the smallest crossing (a grazing face's key is -inf) */
             float kmin = kInf;
 #pragma unroll
-            for (uint32_t f = 0; f < 6; ++f) {
+            for (uint32_t f = 0; f < 6u * kN; ++f) {
                 const bool take = ((cand >> f) & 1u) && !(key[f] >= kmin);
                 kmin = take ? key[f] : kmin;
                 k = take ? f : k;
             }
-            bool act = cand != 0u;
-            if (!kAny) act = act && !(kmin > best.t + kBoxEpsT * (1.f + fabsf(best.t)));
-            if (!wave_any(act)) break;
-            if (act) {
-                cand &= ~(1u << k);
+            act = act && !(kmin > best.t + kBoxEpsT * (1.f + fabsf(best.t)));
+        }
+        if (!wave_any(act)) break;
+        if (act) {
+            cand &= ~(1u << k);
 #pragma unroll
-                for (uint32_t j = 0; j < 2; ++j) {
-                    const DPrim p = sc.box_lds ? load_lds(bt, 2u * k + j) : load_global(bt, 2u * k + j);
-                    float t, u, v;
-                    if (tri_hit(p, ray, t, u, v)) {
-                        if (kAny) {
-                            found = true;
-                        } else if (t < best.t || (t == best.t && p.pad < best_orig)) {
-                            best.t = t; best.u = u; best.v = v; best.prim = (int32_t) (p.type >> 8);
-                            best_orig = p.pad;
-                        }
+            for (uint32_t j = 0; j < 2; ++j) {
+                const DPrim p = sc.box_lds ? load_lds(bt, 2u * k + j) : load_global(bt, 2u * k + j);
+                float t, u, v;
+                if (tri_hit(p, ray, t, u, v)) {
+                    if (kAny) {
+                        found = true;
+                    } else if (t < best.t || (t == best.t && p.pad < best_orig)) {
+                        best.t = t; best.u = u; best.v = v; best.prim = (int32_t) (p.type >> 8);
+                        best_orig = p.pad;
                     }
                 }
-                if (kAny && found) cand = 0u;
             }
+            if (kAny && found) cand = 0u;
         }
     }
+}
+/* kAny: any hit in [0, ray.maxt] (found); else the closest hit (best, best_orig).  The boxes two at a time (12 keys
+ * and a 12-bit candidate word per lane), an odd last one alone. */
+template <bool kAny>
+AD void box_walk(const SceneRef &sc, const Ray &ray, Hit &best, uint32_t &best_orig, bool &found) {
+    const uint32_t nb = ufirst(sc.n_boxes);
+    uint32_t bi = 0;
+    for (; bi + 2u <= nb; bi += 2u) box_rounds<kAny, 2>(sc, bi, ray, best, best_orig, found);
+    if (bi < nb) box_rounds<kAny, 1>(sc, bi, ray, best, best_orig, found);
 }
 
 /* Two records in flight (a, b), each reloaded in place right after its own test: the next
