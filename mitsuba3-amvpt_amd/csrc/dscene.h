@@ -117,7 +117,12 @@ struct DView {
 
 /* Small material/shape/emitter/view tables are copied to LDS by every kernel. */
 constexpr uint32_t kTabBytes = 8192, kViewTabBytes = 8192;
-inline __host__ __device__ uint32_t tab_round(uint32_t b) { return (b + 15u) & ~15u; }
+#if defined(__HIPCC__)
+#define DSHD __host__ __device__
+#else
+#define DSHD   /* plain C++ (scene_image.cpp) */
+#endif
+inline DSHD uint32_t tab_round(uint32_t b) { return (b + 15u) & ~15u; }
 
 /*
  * A box mesh (a `cube` shape, or any 12-triangle mesh whose triangles tile the faces of a parallelepiped):
@@ -151,7 +156,7 @@ struct DScene {
     uint32_t lds_bytes;     /* nodes+prims footprint (LDS staging when small) */
     uint32_t n_bsdfs;
     uint32_t tab_bytes;     /* shapes+bsdfs+emitters footprint if <= kTabBytes (staged in LDS), else 0 */
-    uint32_t oct_stride;    /* != 0: nodes[] holds 8 direction-octant orderings of n_nodes each (amvpt_capi.cpp) */
+    uint32_t oct_stride;    /* != 0: nodes[] holds 8 direction-octant orderings of n_nodes each (scene_image.cpp) */
     /* the spheres' primitive indices in scene order of their ordinals (a sphere record's `face` field holds its
      * ordinal): the wave-uniform walks' deferred sphere tests (dgeom.h, kSph = 2) */
     const uint32_t *sph_prims;
@@ -163,7 +168,7 @@ struct DScene {
     const DPrim *loose_prims;
     uint32_t n_boxes, n_loose;
     uint32_t n_loose_rect, n_loose_tri;   /* loose_prims: rectangles, then triangles, then spheres */
-    /* BVH scenes: the rectangles kept out of the BVH (amvpt_capi.cpp, at most kOuterMax), each record's
+    /* BVH scenes: the rectangles kept out of the BVH (scene_image.cpp, at most kOuterMax), each record's
      * `type` | its index in prims[] << 8 (they follow the BVH's primitives there); n_outer = 0: none */
     const DPrim *outer;
     uint32_t n_outer;

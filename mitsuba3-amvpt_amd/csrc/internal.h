@@ -1,6 +1,7 @@
 /*
- * internal.h -- host-side state shared by the C-ABI (amvpt_capi.cpp) and the
- * kernel launcher (amvpt_render.hip).  Not part of the public interface.
+ * internal.h -- host-side state shared by the C-ABI (amvpt_capi.cpp), the scene
+ * image build (scene_image.cpp) and the kernel launcher (amvpt_render.hip).  Not
+ * part of the public interface.
  */
 #pragma once
 #include <string>
@@ -10,10 +11,9 @@
 #include "../../include/amvpt_fixed.h"
 #include "dscene.h"
 
-struct amvpt_scene {
-    amvpt::DScene dev;          /* device pointers */
-    void *dev_scene_struct = nullptr; /* device copy of `dev` */
-    std::vector<void *> allocations;
+namespace amvpt {
+/* what the host keeps about a scene next to its device tables: filled by the scene image build (scene_image.h) */
+struct SceneFacts {
     uint32_t n_nodes = 0, n_prims = 0;
     uint32_t n_sph = 0;         /* spheres (<= 64: the wave-uniform walks defer their float64 tests) */
     uint32_t n_outer = 0;       /* rectangles kept out of the BVH (DScene::outer) */
@@ -24,11 +24,18 @@ struct amvpt_scene {
     float root_lo[3] = {0, 0, 0}, root_hi[3] = {0, 0, 0};   /* the BVH root box (ray binning's grid) */
     bool has_spheres = false;   /* the brute-force suffix walks take their sphere-free instances otherwise */
     bool all_diffuse = false;   /* every BSDF is plain `diffuse`: kernels take their kDiff instances */
+};
+} // namespace amvpt
+
+struct amvpt_scene : amvpt::SceneFacts {
+    amvpt::DScene dev;          /* device pointers */
+    void *dev_scene_struct = nullptr; /* device copy of `dev` */
+    std::vector<void *> allocations;
     int device = 0;
 };
 
 namespace amvpt {
-void set_error(const std::string &msg);
+void set_error(const std::string &msg);   /* amvpt_capi.cpp (the test driver has its own) */
 amvpt_status hip_fail(const char *what, int err);
 amvpt_status render_impl(amvpt_scene *scene, const amvpt_view_desc *views, const amvpt_params *params,
                          const amvpt_lane_set &lanes, const amvpt_film_window &film, void *stream,
