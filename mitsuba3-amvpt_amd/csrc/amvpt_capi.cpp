@@ -146,7 +146,7 @@ amvpt_status amvpt_scene_create(const amvpt_scene_desc *d, amvpt_scene **out) {
         row(img.emitters, D.emitters), row(img.vpos, D.vpos), row(img.vnrm, D.vnrm), row(img.vuv, D.vuv),
         row(img.faces, D.faces), row(img.face_area, D.face_area), row(img.sph_prims, D.sph_prims),
         row(img.boxes, D.boxes), row(img.box_prims, D.box_prims), row(img.loose_prims, D.loose_prims),
-        row(img.outer, D.outer), row(img.nodes2, D.nodes2), row(img.nodes2h, D.nodes2h)};
+        row(img.outer, D.outer), row(img.nodes2, D.nodes2), row(img.nodes2h, D.nodes2h), row(img.hrec, D.hrec)};
     for (const Upload &u : table) {
         void *p = nullptr;
         if ((st = upload(u.src, u.bytes, &p)) != AMVPT_OK) break;

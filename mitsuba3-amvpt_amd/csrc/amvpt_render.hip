@@ -437,7 +437,7 @@ AD float4 hit_rec(const Hit &h) { return make_float4(h.t, h.u, h.v, bitsf((uint3
 /* SurfaceInteraction::emitter: the shape's area emitter, or the scene's environment (constant)
  * emitter for a ray that left the scene */
 AD int32_t si_emitter(const SceneRef &sc, const SI &si) {
-    return si.valid() ? sc.g->shapes[si.shape].emitter : sc.g->environment;
+    return si.valid() ? si.emitter : sc.g->environment;
 }
 
 /* AreaLight::eval (area.cpp:82-88: front side only), ConstantBackgroundEmitter::eval
@@ -2115,7 +2115,7 @@ AD bool bounce_vertex(const KParams &P, const DScene &S, const SceneRef &sc, Pat
         s.res = cfma(s.thr, emitter_eval(sc, em, si, s.prev_pdf > 0.f) * mis_bsdf, s.res);
     }
     bool active_next = (s.depth + 1 < P.max_depth) && si.valid();
-    int32_t b = si.valid() ? S.shapes[si.shape].bsdf : -1;
+    int32_t b = si.valid() ? si.bsdf : -1;
     bool active_em = active_next && (bsdf_flags(S.bsdfs, b) & BF_Smooth);
     float e1 = rng.next_1d(), e2 = rng.next_1d();
     {
@@ -2606,7 +2606,7 @@ AD void prim_requests(const KParams &P, const SceneRef &sc, const DScene &S, con
         const SI si = compute_si(sc, pr.ray, hit);
         const bool p_hit = si.valid();
         const bool direct_em = si_emitter(sc, si) >= 0;
-        const int32_t b = p_hit ? S.shapes[si.shape].bsdf : -1;
+        const int32_t b = p_hit ? si.bsdf : -1;
         const bool bsdf_smooth = (bsdf_flags(S.bsdfs, b) & BF_Smooth) != 0;
         const float e1 = pr.rng.next_1d(), e2 = pr.rng.next_1d();
         DSamp ds;
@@ -2920,7 +2920,7 @@ AD void mv_primary_lane(const KParams &P, const DScene &S, const SceneRef &sc, c
             bool direct_em = em >= 0;
             C3 emitted = c3(0.f);
             if (direct_em) emitted = emitter_eval(sc, em, si, true);
-            int32_t b = p_hit ? S.shapes[si.shape].bsdf : -1;
+            int32_t b = p_hit ? si.bsdf : -1;
             bool bsdf_smooth = (bsdf_flags(S.bsdfs, b) & BF_Smooth) != 0;
             bool active_em = p_hit && bsdf_smooth;
             float e1 = rng.next_1d(), e2 = rng.next_1d();

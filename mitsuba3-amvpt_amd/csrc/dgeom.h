@@ -1118,13 +1118,25 @@ struct SI {
     f3 p, n;
     Frame3 sh;
     f3 wi;
-    int32_t shape;
+    int32_t shape, bsdf, emitter;   /* the shape and its BSDF / area emitter ids; -1 off a surface */
     AD bool valid() const { return t != kInf; }
 };
 
+/* a lane's hit record (dscene.h DHitRec: 7 rows of 16 B) in device memory: one address per record, its words at
+ * constant offsets from it.  Word loads, so that only the words a path reads are fetched (the backend merges
+ * neighbours into dwordx2 / x3 / x4 loads) */
+struct HRow { float x, y, z, w; };
+typedef __attribute__((address_space(1))) const uint32_t *HRecPtr;
+AD HRecPtr hrec_at(const DHitRec *tab, uint32_t prim) {
+    return (HRecPtr) (uintptr_t) tab + (size_t) prim * (sizeof(DHitRec) / 4);
+}
+AD HRow hrec_row(HRecPtr rec, uint32_t k) {
+    return HRow{bitsf(rec[4 * k]), bitsf(rec[4 * k + 1]), bitsf(rec[4 * k + 2]), bitsf(rec[4 * k + 3])};
+}
+
 AD SI compute_si(const SceneRef &sc, const Ray &ray, const Hit &h) {
     SI si;
-    si.shape = -1;
+    si.shape = si.bsdf = si.emitter = -1;
     if (h.prim < 0) {
         si.t = kInf;
         si.p = mk(0.f, 0.f, 0.f);
@@ -1133,66 +1145,56 @@ AD SI compute_si(const SceneRef &sc, const Ray &ray, const Hit &h) {
         si.wi = -ray.d;
         return si;
     }
-    const DPrim pr = sc.prims[h.prim];
-    const DShape &s = sc.g->shapes[pr.shape];
-    si.shape = (int32_t) pr.shape;
+    /* the primitive's hit record (DHitRec): the head row, then the rows its type reads */
+    const HRecPtr rec = hrec_at(sc.g->hrec, (uint32_t) h.prim);
+    const HRow hd = hrec_row(rec, 0);
+    const uint32_t kind = fbits(hd.x), type = kind & kHitTypeMask;
+    si.shape = (int32_t) fbits(hd.y);
+    si.bsdf = (int32_t) fbits(hd.z);
+    si.emitter = (int32_t) fbits(hd.w);
     si.t = h.t;
     f3 dp_du;
-    if (pr.type == PRIM_RECT) {
+    if (type == PRIM_RECT) {
+        const HRow r0 = hrec_row(rec, 1), r1 = hrec_row(rec, 2), r2 = hrec_row(rec, 3);
         f3 p = ray_at(ray, h.t);
-        f3 tr = mk(s.to_world[3], s.to_world[7], s.to_world[11]);
-        f3 fn = ld3(s.frame_n);
+        f3 tr = mk(r0.x, r0.y, r0.z);
+        f3 fn = mk(r1.x, r1.y, r1.z);
         float dist = dot(tr - p, fn);
         si.p = p + dist * fn;
         si.n = fn;
         si.sh.n = fn;
-        dp_du = ld3(s.frame_s);
-    } else if (pr.type == PRIM_TRI) {
-        /* the record's fourth words: vbase + faces[3 (fbase + face) + k] (amvpt_capi.cpp) */
-        const uint32_t i0 = fbits(pr.a[3]), i1 = fbits(pr.b[3]), i2 = fbits(pr.c[3]);
-        f3 p0 = ld3(sc.g->vpos + 3 * (size_t) i0), p1 = ld3(sc.g->vpos + 3 * (size_t) i1),
-           p2 = ld3(sc.g->vpos + 3 * (size_t) i2);
+        dp_du = mk(r2.x, r2.y, r2.z);
+    } else if (type == PRIM_TRI) {
+        const HRow r0 = hrec_row(rec, 1), r1 = hrec_row(rec, 2), r2 = hrec_row(rec, 3);
+        const HRow q0 = hrec_row(rec, 4), q1 = hrec_row(rec, 5), q2 = hrec_row(rec, 6);
+        f3 p0 = mk(r0.x, r0.y, r0.z), p1 = mk(r1.x, r1.y, r1.z), p2 = mk(r2.x, r2.y, r2.z);
         float b1 = h.u, b2 = h.v, b0 = 1.f - b1 - b2;
         si.p = fma3(p0, b0, fma3(p1, b1, p2 * b2));
-        si.n = normalize(cross(p1 - p0, p2 - p0));
-        f3 dpdv;
-        coord_sys(si.n, dp_du, dpdv);
-        if (s.has_uv) {
-            const float *uv = sc.g->vuv;
-            float u0x = uv[2 * i0], u0y = uv[2 * i0 + 1], u1x = uv[2 * i1], u1y = uv[2 * i1 + 1],
-                  u2x = uv[2 * i2], u2y = uv[2 * i2 + 1];
-            float d0x = u1x - u0x, d0y = u1y - u0y, d1x = u2x - u0x, d1y = u2y - u0y;
-            float det = fmsub(d0x, d1y, d0y * d1x), inv_det = rcp(det);
-            if (det != 0.f) {
-                f3 dp0 = p1 - p0, dp1 = p2 - p0;
-                dp_du = mk(fmsub(d1y, dp0.x, d0y * dp1.x) * inv_det, fmsub(d1y, dp0.y, d0y * dp1.y) * inv_det,
-                           fmsub(d1y, dp0.z, d0y * dp1.z) * inv_det);
-            }
-        }
-        if (s.has_normals) {
-            f3 n0 = ld3(sc.g->vnrm + 3 * (size_t) i0), n1 = ld3(sc.g->vnrm + 3 * (size_t) i1),
-               n2 = ld3(sc.g->vnrm + 3 * (size_t) i2);
+        si.n = mk(r0.w, r1.w, r2.w);       /* normalize(cross(p1 - p0, p2 - p0)), negated for a flipped shape */
+        dp_du = mk(q0.w, q1.w, q2.w);      /* the UV tangent, or coord_sys's s of the unflipped normal */
+        if (kind & kHitNormals) {
+            f3 n0 = mk(q0.x, q0.y, q0.z), n1 = mk(q1.x, q1.y, q1.z), n2 = mk(q2.x, q2.y, q2.z);
             f3 n = fma3(n2, b2, fma3(n1, b1, n0 * b0));
             float il = rsqrt_(sqnorm(n));
             si.sh.n = n * il;
+            if (kind & kHitFlip) si.sh.n = -si.sh.n;
         } else {
             si.sh.n = si.n;
         }
-        if (s.flip) { si.n = -si.n; si.sh.n = -si.sh.n; }
     } else {
-        f3 c = ld3(s.center);
+        const HRow r0 = hrec_row(rec, 1), r1 = hrec_row(rec, 2), r2 = hrec_row(rec, 3);
+        const HRow q0 = hrec_row(rec, 4), q1 = hrec_row(rec, 5), q2 = hrec_row(rec, 6);
+        f3 c = mk(r0.x, r0.y, r0.z);
         si.sh.n = normalize(ray_at(ray, h.t) - c);
-        si.p = fma3(si.sh.n, s.radius, c);
-        const float *to = s.to_object;
-        f3 local = {fmadd(to[2], si.p.z, fmadd(to[1], si.p.y, fmadd(to[0], si.p.x, to[3]))),
-                    fmadd(to[6], si.p.z, fmadd(to[5], si.p.y, fmadd(to[4], si.p.x, to[7]))),
-                    fmadd(to[10], si.p.z, fmadd(to[9], si.p.y, fmadd(to[8], si.p.x, to[11])))};
-        dp_du = mk(-local.y, local.x, 0.f);
-        const float *tw = s.to_world;
-        dp_du = mk(fmadd(tw[2], dp_du.z, fmadd(tw[1], dp_du.y, tw[0] * dp_du.x)),
-                   fmadd(tw[6], dp_du.z, fmadd(tw[5], dp_du.y, tw[4] * dp_du.x)),
-                   fmadd(tw[10], dp_du.z, fmadd(tw[9], dp_du.y, tw[8] * dp_du.x))) * (2.f * kPi);
-        if (s.flip) si.sh.n = -si.sh.n;
+        si.p = fma3(si.sh.n, r0.w, c);
+        /* to_object's rows 0, 1 (the local z is not read), then to_world's linear part */
+        const float lx = fmadd(r1.z, si.p.z, fmadd(r1.y, si.p.y, fmadd(r1.x, si.p.x, r1.w))),
+                    ly = fmadd(r2.z, si.p.z, fmadd(r2.y, si.p.y, fmadd(r2.x, si.p.x, r2.w)));
+        dp_du = mk(-ly, lx, 0.f);
+        dp_du = mk(fmadd(q0.z, dp_du.z, fmadd(q0.y, dp_du.y, q0.x * dp_du.x)),
+                   fmadd(q1.z, dp_du.z, fmadd(q1.y, dp_du.y, q1.x * dp_du.x)),
+                   fmadd(q2.z, dp_du.z, fmadd(q2.y, dp_du.y, q2.x * dp_du.x))) * (2.f * kPi);
+        if (kind & kHitFlip) si.sh.n = -si.sh.n;
         si.n = si.sh.n;
     }
     /* initialize_sh_frame */

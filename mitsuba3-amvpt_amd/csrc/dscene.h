@@ -6,6 +6,7 @@
  * and are staged into LDS at kernel start when they fit (kLdsSceneBytes):
  *   nodes[]   binary BVH, 32 B per node                (replaces Embree, scene_embree.inl)
  *   prims[]   BVH-ordered primitives, 64 B each        (rectangle / triangle / sphere)
+ *   hrec[]    per-primitive hit records, 112 B each       (what compute_si reads; built once on the host)
  *   shapes[]  per-shape transforms, frames, mesh bases (rectangle.cpp, mesh.cpp, sphere.cpp)
  *   bsdfs[]   flattened BSDF parameters                (diffuse / roughconductor / twosided)
  *   emitters[] area lights                             (area.cpp)
@@ -71,6 +72,26 @@ struct alignas(16) DPrim {
     uint32_t type, shape, face;
     uint32_t pad;            /* scene-order primitive index: closest-hit tie-break */
 };
+
+/*
+ * What compute_si needs of a hit, one record per entry of prims[] (same index: Hit::prim), 7 x 16 B = 112 B.  The
+ * record is self-contained -- a hit's shading reads it and no other geometry table -- and everything in it that
+ * does not depend on the hit point is computed once on the host (scene_image.cpp build_hit_records), with the
+ * kernels' own operation sequences (dmath.h), so the bits are the ones a lane used to compute per hit.
+ *   row 0        kind = PRIM_* | flags (kHitFlip, kHitNormals), shape, the shape's bsdf, the shape's emitter
+ *   rectangle    r[0].xyz to_world's translation, r[1].xyz frame_n, r[2].xyz frame_s
+ *   triangle     r[0..2].xyz p0, p1, p2 (the vpos values); r[0..2].w the geometric normal, negated when the
+ *                shape flips (negation is exact); r[3..5].xyz the vertex normals n0, n1, n2 (kHitNormals, else 0);
+ *                r[3..5].w dp_du: the UV form when the mesh has UVs and det != 0, else coordinate_system's s
+ *   sphere       r[0] = (centre, radius), r[1], r[2] rows 0, 1 of to_object, r[3..5].xyz rows 0..2 of to_world's
+ *                linear part
+ */
+struct alignas(16) DHitRec {
+    uint32_t kind, shape;
+    int32_t bsdf, emitter;
+    float r[6][4];
+};
+constexpr uint32_t kHitTypeMask = 0xffu, kHitFlip = 0x100u, kHitNormals = 0x200u;
 
 struct DShape {
     uint32_t type, flip;
@@ -178,6 +199,7 @@ struct DScene {
     uint32_t n_nodes2;
     const DNode2h *nodes2h;       /* the float16 form of nodes2, what the walks read, in the normalized frame: */
     float n2_center[3], n2_scale; /*   x' = (x - n2_center) * n2_scale */
+    const DHitRec *hrec;          /* one per entry of prims[]: what compute_si reads of a hit */
 };
 constexpr uint32_t kOuterMax = 8;
 

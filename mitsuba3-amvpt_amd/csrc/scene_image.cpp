@@ -369,8 +369,8 @@ static void add_mesh(const amvpt_shape_desc &s, uint32_t i, DShape &o, SceneImag
                     *P2 = s.positions + 3 * s.faces[3 * f + 2];
         /* p0 and the two edges (the f32 differences tri_hit would form: same bits) */
         for (int k = 0; k < 3; ++k) { p.a[k] = P0[k]; p.b[k] = P1[k] - P0[k]; p.c[k] = P2[k] - P0[k]; }
-        /* the spare fourth words: the face's absolute vertex indices (compute_si reads the vertices without
-         * a dependent load of the face table) */
+        /* the spare fourth words: the face's absolute vertex indices (the hit records are built from them:
+         * triangle_record) */
         for (int k = 0; k < 3; ++k) {
             const uint32_t vi = o.vbase + s.faces[3 * f + k];
             std::memcpy(k == 0 ? &p.a[3] : k == 1 ? &p.b[3] : &p.c[3], &vi, 4);
@@ -605,7 +605,75 @@ static void number_spheres(SceneImage &img) {
     img.dev.n_sph = img.facts.n_sph = (uint32_t) img.sph_prims.size();
 }
 
-static constexpr uint32_t kBrutePrimsHost = 48;   /* dgeom.h kBrutePrims: brute-force scenes have no BVH walk */
+/* ---- hit records (dscene.h DHitRec): the hit-independent part of compute_si (dgeom.h), operation for operation
+ * as the kernels formed it per hit -- fmaf where dmath.h has fmadd / fmsub, 1.0f / sqrt for rsqrt_, 1.0f / x for
+ * rcp, the same operand order (this unit is built with -ffp-contract=off) ---- */
+static inline uint32_t hbits(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
+static inline float hfloat(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
+static inline float hmulsign(float a, float b) { return hfloat(hbits(a) ^ (hbits(b) & 0x80000000u)); }
+static inline float hmulsign_neg(float a, float b) { return hfloat(hbits(a) ^ (~hbits(b) & 0x80000000u)); }
+/* the s of coord_sys (dmath.h; vector.h:116-136) */
+static void hcoord_s(const float *n, float *s) {
+    const float sg = hmulsign(1.f, n[2]), a = -(1.0f / (sg + n[2])), b = n[0] * n[1] * a;
+    s[0] = hmulsign((n[0] * n[0]) * a, n[2]) + 1.f;
+    s[1] = hmulsign(b, n[2]);
+    s[2] = hmulsign_neg(n[0], n[2]);
+}
+
+static void triangle_record(const SceneImage &img, const DPrim &p, const DShape &s, DHitRec &h) {
+    const uint32_t vi[3] = {hbits(p.a[3]), hbits(p.b[3]), hbits(p.c[3])};   /* absolute vertex indices (add_mesh) */
+    const float *P[3] = {&img.vpos[3 * (size_t) vi[0]], &img.vpos[3 * (size_t) vi[1]], &img.vpos[3 * (size_t) vi[2]]};
+    float e1[3], e2[3], c[3], n[3], dp_du[3];
+    for (int k = 0; k < 3; ++k) { e1[k] = P[1][k] - P[0][k]; e2[k] = P[2][k] - P[0][k]; }
+    hcross(e1, e2, c);
+    const float il = 1.0f / std::sqrt(hdot(c, c));
+    for (int k = 0; k < 3; ++k) n[k] = c[k] * il;
+    hcoord_s(n, dp_du);
+    if (s.has_uv) {
+        const float *u0 = &img.vuv[2 * (size_t) vi[0]], *u1 = &img.vuv[2 * (size_t) vi[1]], *u2 = &img.vuv[2 * (size_t) vi[2]];
+        const float d0x = u1[0] - u0[0], d0y = u1[1] - u0[1], d1x = u2[0] - u0[0], d1y = u2[1] - u0[1];
+        const float det = std::fmaf(d0x, d1y, -(d0y * d1x));
+        if (det != 0.f) {
+            const float inv_det = 1.0f / det;
+            for (int k = 0; k < 3; ++k) dp_du[k] = std::fmaf(d1y, e1[k], -(d0y * e2[k])) * inv_det;
+        }
+    }
+    if (s.has_normals) h.kind |= kHitNormals;
+    for (int v = 0; v < 3; ++v) {
+        for (int k = 0; k < 3; ++k) {
+            h.r[v][k] = P[v][k];
+            h.r[3 + v][k] = s.has_normals ? img.vnrm[3 * (size_t) vi[v] + k] : 0.f;
+        }
+        h.r[v][3] = s.flip ? -n[v] : n[v];
+        h.r[3 + v][3] = dp_du[v];
+    }
+}
+
+/* step 9: one hit record per primitive, in prims[] order */
+static void build_hit_records(SceneImage &img) {
+    img.hrec.resize(img.prims.size());
+    for (uint32_t i = 0; i < img.facts.n_prims; ++i) {
+        const DPrim &p = img.prims[i];
+        const DShape &s = img.shapes[p.shape];
+        DHitRec &h = img.hrec[i];
+        std::memset(&h, 0, sizeof(h));
+        h.kind = p.type | (s.flip ? kHitFlip : 0u);
+        h.shape = p.shape; h.bsdf = s.bsdf; h.emitter = s.emitter;
+        if (p.type == PRIM_RECT) {
+            for (int k = 0; k < 3; ++k) { h.r[0][k] = s.to_world[4 * k + 3]; h.r[1][k] = s.frame_n[k]; h.r[2][k] = s.frame_s[k]; }
+        } else if (p.type == PRIM_TRI) {
+            triangle_record(img, p, s, h);
+        } else {
+            std::memcpy(h.r[0], s.center, 12);
+            h.r[0][3] = s.radius;
+            std::memcpy(h.r[1], s.to_object, 16);
+            std::memcpy(h.r[2], s.to_object + 4, 16);
+            for (int k = 0; k < 3; ++k) std::memcpy(h.r[3 + k], s.to_world + 4 * k, 12);
+        }
+    }
+}
+
+static constexpr uint32_t kBrutePrimsHost = 48;  /* dgeom.h kBrutePrims: brute-force scenes have no BVH walk */
 /*
  * Box meshes (dscene.h DBox): a mesh shape of 12 triangles whose vertices map, through the shape's
  * to_object (in double), to corners of [-1, 1]^3 within 1e-5, every triangle lying in one face plane, two
@@ -713,7 +781,7 @@ static void build_boxes(const amvpt_scene_desc *d, SceneImage &img) {
     }
 }
 
-/* step 9: the remaining scalars, then one zero element in every empty table (keep a valid pointer) */
+/* step 10: the remaining scalars, then one zero element in every empty table (keep a valid pointer) */
 static void finish(const amvpt_scene_desc *d, const Work &w, SceneImage &img) {
     DScene &D = img.dev;
     SceneFacts &F = img.facts;
@@ -737,7 +805,7 @@ static void finish(const amvpt_scene_desc *d, const Work &w, SceneImage &img) {
     auto keep = [](auto &v, size_t n) { if (v.empty()) v.resize(n); };   /* n zero elements */
     keep(img.vpos, 3); keep(img.vnrm, 3); keep(img.vuv, 2); keep(img.faces, 3); keep(img.face_area, 2);
     keep(img.outer, 1); keep(img.sph_prims, 1); keep(img.boxes, 1); keep(img.box_prims, 1); keep(img.loose_prims, 1);
-    keep(img.nodes2, 1); keep(img.nodes2h, 1);
+    keep(img.nodes2, 1); keep(img.nodes2h, 1); keep(img.hrec, 1);
 }
 
 /* the steps keep this order: each reads what the ones before it left */
@@ -754,6 +822,7 @@ amvpt_status build_scene_image(const amvpt_scene_desc *d, uint32_t max_leaf, flo
     build_emitters(d, img);
     number_spheres(img);
     build_boxes(d, img);
+    build_hit_records(img);
     finish(d, w, img);
     return AMVPT_OK;
 }

@@ -20,7 +20,8 @@ struct SceneImage {
     std::vector<DBox> boxes;
     std::vector<DNode2> nodes2;
     std::vector<DNode2h> nodes2h;
-    DScene dev{};       /* every scalar set, every pointer null */
+    std::vector<DHitRec> hrec;   /* one per entry of prims[] */
+    DScene dev{};      /* every scalar set, every pointer null */
     SceneFacts facts;
 };
 
