@@ -129,6 +129,21 @@ class DenoiseParams(ctypes.Structure):
                 % self.values())
 
 
+class TemporalParams(ctypes.Structure):
+    """amvpt_temporal_params (include/amvpt_temporal.h).  Without arguments: amvpt_temporal_default_params' values,
+    {32, 0.02, 0.9}; plane_tol is in world units."""
+    _fields_ = [("max_history", u32), ("plane_tol", f32), ("normal_cos", f32)]
+
+    def __init__(self, max_history=32, plane_tol=0.02, normal_cos=0.9):
+        super().__init__(max_history, plane_tol, normal_cos)
+
+    def values(self):
+        return (self.max_history, self.plane_tol, self.normal_cos)
+
+    def __repr__(self):
+        return "TemporalParams(max_history=%r, plane_tol=%r, normal_cos=%r)" % self.values()
+
+
 # amvpt_run_exchange_fn: (ctx, n_runs, *run_lane_begin, *run_count, *run_prefix, *total) -> 0 on success
 RunExchangeFn = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, u32, ctypes.POINTER(u64), ctypes.POINTER(u64),
                                  ctypes.POINTER(u64), ctypes.POINTER(u64))
@@ -260,6 +275,16 @@ def hip_lib():
             L.amvpt_denoise.restype = L.amvpt_denoise_host.restype = ctypes.c_int
             L.amvpt_denoise.argtypes = [vp, u32, u32, u32, vp, ctypes.POINTER(DenoiseParams), vp, vp, vp]
             L.amvpt_denoise_host.argtypes = [vp, u32, u32, u32, vp, ctypes.POINTER(DenoiseParams), vp, vp]
+        if hasattr(L, "amvpt_temporal_version"):   # include/amvpt_temporal.h
+            vp = ctypes.c_void_p
+            L.amvpt_temporal_version.restype = u32
+            L.amvpt_temporal_default_params.restype = TemporalParams
+            L.amvpt_temporal_default_params.argtypes = []
+            L.amvpt_temporal.restype = L.amvpt_temporal_host.restype = ctypes.c_int
+            planes = [vp, u32, vp, vp, vp, vp, vp, ctypes.POINTER(Params), ctypes.POINTER(u32 * 4),
+                      ctypes.POINTER(TemporalParams), vp, vp]
+            L.amvpt_temporal.argtypes = planes + [vp]
+            L.amvpt_temporal_host.argtypes = planes
         _hip = L
     return _hip
 
@@ -309,6 +334,62 @@ def denoise_sigma_plane(guides):
     pts = g[g[:, 0] >= 0][:, 4:7]
     side = np.float32((pts.max(axis=0) - pts.min(axis=0)).max()) if len(pts) else np.float32(0)
     return float(side / np.float32(40)) if side > 0 else 0.05
+
+
+def temporal_version():
+    """AMVPT_TEMPORAL_VERSION of the loaded library (include/amvpt_temporal.h)."""
+    return hip_lib().amvpt_temporal_version()
+
+
+def temporal_default_params():
+    """amvpt_temporal_default_params of the loaded library."""
+    c = hip_lib().amvpt_temporal_default_params()
+    return TemporalParams(*c.values())
+
+
+def _views_ptr(views):
+    return ctypes.cast(views, ctypes.c_void_p) if views is not None else None
+
+
+def _rect_ref(rect):
+    return ctypes.byref((u32 * 4)(*[int(v) for v in rect])) if rect is not None else None
+
+
+def temporal_device(image_ptr, channels, guides_ptr, hist_image_ptr, hist_guides_ptr, hist_count_ptr, prev_views, params,
+                    out_image_ptr, out_count_ptr, tp=None, rect=None, stream=None):
+    """amvpt_temporal over device pointers, ordered on `stream`: the current developed image and guide records, the
+    previous call's outputs (image, guide records, count) and the host ViewDesc table the history was rendered with
+    -> out_image_ptr, out_count_ptr.  `params` gives the quilt layout; `rect` = (x0, y0, w, h), whole tiles of the
+    quilt that every plane holds alone (None: all of it)."""
+    L = hip_lib()
+    q = tp if tp is not None else temporal_default_params()
+    _check(L.amvpt_temporal(ctypes.c_void_p(image_ptr), channels, ctypes.c_void_p(guides_ptr),
+                            ctypes.c_void_p(hist_image_ptr), ctypes.c_void_p(hist_guides_ptr),
+                            ctypes.c_void_p(hist_count_ptr), _views_ptr(prev_views), ctypes.byref(params), _rect_ref(rect),
+                            ctypes.byref(q), ctypes.c_void_p(out_image_ptr), ctypes.c_void_p(out_count_ptr),
+                            ctypes.c_void_p(stream or 0)), L)
+
+
+def temporal_host(image, guides, hist_image, hist_guides, hist_count, prev_views, params, tp=None, rect=None):
+    """amvpt_temporal_host over numpy: (H, W, 3 or 4) float32 image, (H, W, 8) guide records, the history planes of
+    the same size ((H, W, C), (H, W, 8), (H, W)) and the host ViewDesc table of the history -> (image, count).
+    Bit-identical to the device entry; needs no device."""
+    L = hip_lib()
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    g = np.ascontiguousarray(guides, dtype=np.float32)
+    hi = np.ascontiguousarray(hist_image, dtype=np.float32)
+    hg = np.ascontiguousarray(hist_guides, dtype=np.float32)
+    hc = np.ascontiguousarray(hist_count, dtype=np.float32)
+    if img.ndim != 3 or g.shape != img.shape[:2] + (8,):
+        raise ValueError("temporal_host: an (H, W, C) image and (H, W, 8) guide records of its size are needed")
+    if hi.shape != img.shape or hg.shape != g.shape or hc.size != g.shape[0] * g.shape[1]:
+        raise ValueError("temporal_host: the history planes must have the sizes of the image, the guides and (H, W)")
+    q = tp if tp is not None else temporal_default_params()
+    out, cnt = np.empty_like(img), np.empty(img.shape[:2], dtype=np.float32)
+    _check(L.amvpt_temporal_host(img.ctypes.data, img.shape[2], g.ctypes.data, hi.ctypes.data, hg.ctypes.data,
+                                 hc.ctypes.data, _views_ptr(prev_views), ctypes.byref(params), _rect_ref(rect),
+                                 ctypes.byref(q), out.ctypes.data, cnt.ctypes.data), L)
+    return out, cnt
 
 
 def guides_version():
@@ -928,3 +1009,88 @@ class DeviceScene:
         if getattr(self, "h", None):
             self._lib.amvpt_scene_destroy(self.h)
             self.h = None
+
+
+class TemporalAccumulator:
+    """Temporal accumulation over a sequence of frames (include/amvpt_temporal.h).  It owns two sets of the three
+    planes (accumulated image, guide records, history count) as torch device tensors and the views of the last frame;
+    `push` takes the current developed frame, runs amvpt_guides and amvpt_temporal on the device and swaps the sets.
+    A change of film size, channel count or n_views starts over, as `reset` does."""
+
+    def __init__(self, params=None):
+        self.params = params if params is not None else temporal_default_params()
+        self._scene = None   # (Scene, DeviceScene) of device_scene_for
+        self.reset()
+
+    def device_scene_for(self, scene, scene_desc):
+        """The DeviceScene this accumulator keeps for the loaded `scene` (amvpt.display.display(..., temporal=)):
+        created from `scene_desc` at the first call; another scene replaces it and forgets the history.  reset()
+        keeps it: the geometry does not change with the history."""
+        if self._scene is None or self._scene[0] is not scene:
+            self._scene = (scene, DeviceScene(scene_desc))
+            self.reset()
+        return self._scene[1]
+
+    def reset(self):
+        """Forget the history: the next push returns its frame unchanged, with count 1."""
+        self._key = None
+        self._sets = None
+        self._cur = 0
+        self.prev_views = None
+        self.frames = 0
+
+    @property
+    def image(self):
+        """The accumulated image of the last push, (H, W, C) on the device (None before the first)."""
+        return self._sets[self._cur][0] if self._sets and self.frames else None
+
+    @property
+    def guides(self):
+        """The guide records of the last push, (H, W, 8) on the device."""
+        return self._sets[self._cur][1] if self._sets and self.frames else None
+
+    @property
+    def count(self):
+        """The history count of the last push, (H, W) on the device."""
+        return self._sets[self._cur][2] if self._sets and self.frames else None
+
+    def push(self, device_scene, views, params, image, stream=None):
+        """Accumulate one frame: `image` is the developed frame of `params`' film on the device, a torch tensor
+        (H, W, 3 or 4) or a device pointer (then 4 channels with film_alpha, else 3); `views` the host ViewDesc table
+        it was rendered with.  Work is ordered on `stream` (a hipStream_t handle; None: torch's current stream).
+        Returns the accumulated image, a tensor this accumulator owns: it is the history of the next push and is
+        overwritten by the one after."""
+        import torch
+        h, w = int(params.film_height), int(params.film_width)
+        if hasattr(image, "data_ptr"):
+            if image.dtype != torch.float32 or not image.is_contiguous() or tuple(image.shape[:2]) != (h, w) or image.dim() != 3:
+                raise ValueError("TemporalAccumulator.push: a contiguous float32 (%d, %d, C) tensor is needed" % (h, w))
+            c, ptr = int(image.shape[2]), image.data_ptr()
+        else:
+            c, ptr = (4 if params.film_alpha else 3), int(image)
+        n_views = max(1, int(params.n_views)) if params.multisensor else 1
+        st = torch.cuda.current_stream() if not stream else torch.cuda.ExternalStream(int(stream))
+        with torch.cuda.stream(st):
+            key = (h, w, c, n_views)
+            if key != self._key:
+                self.reset()
+                self._key = key
+                self._sets = [(torch.zeros((h, w, c), dtype=torch.float32, device="cuda"),
+                               torch.zeros((h, w, 8), dtype=torch.float32, device="cuda"),
+                               torch.zeros((h, w), dtype=torch.float32, device="cuda")) for _ in range(2)]
+            hist = self._sets[self._cur]
+            cur = self._sets[1 - self._cur]
+            if self.prev_views is None:   # no history: its count is zero, any valid view table serves
+                hist[2].zero_()
+                prev = views
+            else:
+                prev = self.prev_views
+            device_scene.guides(views, params, cur[1].data_ptr(), stream=st.cuda_stream)
+            temporal_device(ptr, c, cur[1].data_ptr(), hist[0].data_ptr(), hist[1].data_ptr(), hist[2].data_ptr(), prev,
+                            params, cur[0].data_ptr(), cur[2].data_ptr(), tp=self.params, stream=st.cuda_stream)
+        keep = (ViewDesc * n_views)()
+        ctypes.memmove(keep, views, ctypes.sizeof(keep))
+        self.prev_views = keep
+        self._cur = 1 - self._cur
+        self.frames += 1
+        return cur[0]

@@ -163,14 +163,20 @@ def preset_for_scene(scene, sensor=0):
 
 
 def display(scene, preset=None, size=(1280, 720), quilt=False, nearest=False, sensor=0, seed=0, spp=0,
-            counters=None, stream=None, rerender=True, denoise=None):
+            counters=None, stream=None, rerender=True, denoise=None, temporal=None):
     """Render `scene` and run the display stage on the device (amvpt_host_display): render -> develop -> sRGB
     quilt -> lenticular image, one download -> (size[1], size[0], 3) uint8.  preset None: preset_for_scene.
     rerender=False runs the stage alone on the developed frame the last render / display of this sensor left on
     the device (amvpt_host_redisplay_stream): another preset, size or mode for the same frame.
     denoise None: the frame as rendered.  An amvpt.DenoiseParams, or True for amvpt.denoise's defaults, filters the
     developed frame on the device between develop and the sRGB quilt (amvpt_host_denoise_stream); the filtered frame
-    is the cached one afterwards, so with rerender=False a frame already filtered is filtered again."""
+    is the cached one afterwards, so with rerender=False a frame already filtered is filtered again.
+    temporal None: every frame stands alone, and the call and its bytes are what they are without the keyword.  An
+    amvpt.TemporalAccumulator is applied between develop and the denoiser (_display_temporal): the frame is rendered,
+    accumulated, filtered and shown through the C-ABI's device entries, and the accumulator keeps the history."""
+    if temporal is not None:
+        return _display_temporal(scene, temporal, preset, size, quilt, nearest, sensor, seed, spp, counters, stream,
+                                 rerender, denoise)
     _, H = _libs()
     if denoise is not None and denoise is not False:
         if rerender:
@@ -193,6 +199,45 @@ def display(scene, preset=None, size=(1280, 720), quilt=False, nearest=False, se
                                              ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(stream or 0),
                                              ctypes.byref(cnt)), H)
     return out
+
+
+def _display_temporal(scene, acc, preset, size, quilt, nearest, sensor, seed, spp, counters, stream, rerender, denoise):
+    """display with a TemporalAccumulator: render -> develop -> temporal accumulation -> (denoiser) -> sRGB quilt ->
+    lenticular image over torch device tensors; the display image is downloaded once (denoise=True also downloads
+    the guide records, for denoise_sigma_plane; a DenoiseParams does not).  The device scene is a second one beside
+    the host library's, created once per scene and kept on the accumulator (TemporalAccumulator.device_scene_for);
+    the frame the host library caches for rerender=False is not touched."""
+    import torch
+    if not rerender:
+        raise ValueError("display: temporal accumulation needs a fresh frame (rerender=True)")
+    L, _ = _libs()
+    sd, vd, p = scene.describe(sensor, seed, spp)
+    dev = acc.device_scene_for(scene, sd)
+    h, w = int(p.film_height), int(p.film_width)
+    c = 4 if p.film_alpha else 3
+    st = torch.cuda.current_stream() if not stream else torch.cuda.ExternalStream(int(stream))
+    with torch.cuda.stream(st):
+        film = torch.zeros((h, w, c + 1), dtype=torch.float32, device="cuda")
+        img = torch.empty((h, w, c), dtype=torch.float32, device="cuda")
+        dev.render(vd, p, film.data_ptr(), stream=st.cuda_stream, counters=counters)
+        _check_hip(L.amvpt_develop(ctypes.c_void_p(film.data_ptr()), ctypes.c_void_p(img.data_ptr()), w, h, p.film_alpha,
+                                   ctypes.c_void_p(st.cuda_stream)), L)
+        frame = acc.push(dev, vd, p, img, stream=st.cuda_stream)
+        if denoise is not None and denoise is not False:
+            q = denoise if isinstance(denoise, amvpt.DenoiseParams) else amvpt.DenoiseParams(
+                sigma_plane=amvpt.denoise_sigma_plane(acc.guides.cpu().numpy()))
+            out, scratch = torch.empty_like(frame), torch.empty_like(frame)
+            amvpt.denoise_device(frame.data_ptr(), c, w, h, acc.guides.data_ptr(), out.data_ptr(), scratch.data_ptr(), q,
+                                 stream=st.cuda_stream)
+            frame = out
+        q8 = torch.empty((h, w, 3), dtype=torch.uint8, device="cuda")
+        srgb8_device(frame.data_ptr(), c, w, h, q8.data_ptr(), stream=st.cuda_stream)
+        dw, dh = int(size[0]), int(size[1])
+        shown = torch.empty((max(dh, 0), max(dw, 0), 3), dtype=torch.uint8, device="cuda")
+        interlace_device(q8.data_ptr(), w, h, 3, shown.data_ptr(), (dw, dh), preset if preset is not None else
+                         preset_for_scene(scene, sensor), quilt=quilt, nearest=nearest, stream=st.cuda_stream)
+        st.synchronize()
+        return shown.cpu().numpy()
 
 
 def depth_quilt(scene, sensor=0, near=None, far=None):

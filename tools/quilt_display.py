@@ -3,13 +3,15 @@
 
     python tools/quilt_display.py [scene.xml] [-D key=value ...] [--preset NAME --presets presets.csv]
                                   [--size W H] [--nearest] [--out-dir DIR] [--depth PATH]
-                                  [--denoise [ITER]]
+                                  [--denoise [ITER]] [--temporal N]
 
 Without arguments: scenes/cbox_grid.xml at a small resolution, the default preset (LKG4x8) with the scene's view
 grid, a 1280 x 720 display, written to out/<scene>_quilt.png and out/<scene>_display.png.  The frame is rendered once;
 both images come from that frame.  --depth PATH also writes the depth quilt (nearer brighter, background black, scaled to
 the frame's own depth range) as an 8-bit PNG: the RGB-D companion of the quilt.  --denoise [ITER] filters the developed
-frame on the device before both images are made (amvpt.denoise's defaults; ITER iterations instead of 3).
+frame on the device before both images are made (amvpt.denoise's defaults; ITER iterations instead of 3).  --temporal N
+renders N frames at the given spp with consecutive seeds through an amvpt.TemporalAccumulator and shows the last one
+(with --denoise, filtered after the accumulation).
 """
 import argparse
 import os
@@ -33,6 +35,8 @@ def main():
     ap.add_argument("--depth", metavar="PATH", help="also write the depth quilt (amvpt.display.depth_quilt) as a PNG")
     ap.add_argument("--denoise", type=int, nargs="?", const=3, default=None, metavar="ITER",
                     help="filter the frame with the a-trous denoiser (amvpt.denoise), ITER iterations (default 3)")
+    ap.add_argument("--temporal", type=int, default=None, metavar="N",
+                    help="accumulate N frames of consecutive seeds (amvpt.TemporalAccumulator) and show the last")
     a = ap.parse_args()
 
     import amvpt
@@ -54,6 +58,8 @@ def main():
     cnt = amvpt.Counters()
     # one render; the 8-bit quilt from its download (the host entry gives the device's bytes), the display image
     # from the stage run on the frame the render left on the device
+    if a.temporal is not None:
+        return temporal_frames(a, ap, scene, preset, cnt)
     frame = amvpt.render(scene, seed=a.seed, spp=a.spp, counters=cnt)
     if a.denoise is not None:   # the filtered frame replaces the cached one: the display image below shows it
         q = amvpt.denoise_params_for(scene, iterations=a.denoise)
@@ -70,6 +76,27 @@ def main():
     print("%s: quilt %d x %d -> %s_quilt.png, display %d x %d (%s, grid %d x %d) -> %s_display.png, %d lanes" % (
         os.path.basename(a.scene), w, h, stem, a.size[0], a.size[1], used.name, used.grid[0], used.grid[1], stem,
         cnt.lanes))
+
+
+def temporal_frames(a, ap, scene, preset, cnt):
+    """--temporal N: N displays through one accumulator; the quilt is the accumulator's last image."""
+    import amvpt
+    import amvpt.display as D
+    if a.temporal < 1:
+        ap.error("--temporal needs at least one frame")
+    acc = amvpt.TemporalAccumulator()
+    denoise = amvpt.denoise_params_for(scene, iterations=a.denoise) if a.denoise is not None else None
+    for i in range(a.temporal):
+        image = D.display(scene, preset, size=tuple(a.size), nearest=a.nearest, seed=a.seed + i, spp=a.spp, counters=cnt,
+                          denoise=denoise, temporal=acc)
+    os.makedirs(a.out_dir, exist_ok=True)
+    stem = os.path.join(a.out_dir, os.path.splitext(os.path.basename(a.scene))[0])
+    D.write_png(stem + "_quilt.png", D.srgb8(acc.image.cpu().numpy()))
+    D.write_png(stem + "_display.png", image)
+    if a.depth:
+        D.write_png(a.depth, D.depth_quilt(scene))
+    print("%s: %d frames accumulated (mean history %.2f) -> %s_quilt.png, %s_display.png" % (
+        os.path.basename(a.scene), a.temporal, float(acc.count.mean()), stem, stem))
 
 
 if __name__ == "__main__":
