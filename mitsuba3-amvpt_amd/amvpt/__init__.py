@@ -144,6 +144,23 @@ class TemporalParams(ctypes.Structure):
         return "TemporalParams(max_history=%r, plane_tol=%r, normal_cos=%r)" % self.values()
 
 
+class VarianceParams(ctypes.Structure):
+    """amvpt_variance_params (include/amvpt_variance.h).  Without arguments: amvpt_variance_default_params' values,
+    {4, 2.0, 1e-8, 0.05, 5, 4}; sigma_plane is in world units."""
+    _fields_ = [("iterations", u32), ("sigma_lum", f32), ("var_floor", f32), ("sigma_plane", f32),
+                ("normal_squarings", u32), ("min_history", u32)]
+
+    def __init__(self, iterations=4, sigma_lum=2.0, var_floor=1e-8, sigma_plane=0.05, normal_squarings=5, min_history=4):
+        super().__init__(iterations, sigma_lum, var_floor, sigma_plane, normal_squarings, min_history)
+
+    def values(self):
+        return (self.iterations, self.sigma_lum, self.var_floor, self.sigma_plane, self.normal_squarings, self.min_history)
+
+    def __repr__(self):
+        return ("VarianceParams(iterations=%r, sigma_lum=%r, var_floor=%r, sigma_plane=%r, normal_squarings=%r, "
+                "min_history=%r)" % self.values())
+
+
 # amvpt_run_exchange_fn: (ctx, n_runs, *run_lane_begin, *run_count, *run_prefix, *total) -> 0 on success
 RunExchangeFn = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, u32, ctypes.POINTER(u64), ctypes.POINTER(u64),
                                  ctypes.POINTER(u64), ctypes.POINTER(u64))
@@ -285,6 +302,21 @@ def hip_lib():
                       ctypes.POINTER(TemporalParams), vp, vp]
             L.amvpt_temporal.argtypes = planes + [vp]
             L.amvpt_temporal_host.argtypes = planes
+        if hasattr(L, "amvpt_variance_version"):   # include/amvpt_variance.h
+            vp = ctypes.c_void_p
+            vq = ctypes.POINTER(VarianceParams)
+            L.amvpt_variance_version.restype = u32
+            L.amvpt_variance_default_params.restype = VarianceParams
+            L.amvpt_variance_default_params.argtypes = []
+            planes = [vp, u32, vp, vp, vp, vp, vp, vp, ctypes.POINTER(Params), ctypes.POINTER(u32 * 4),
+                      ctypes.POINTER(TemporalParams), vp, vp, vp]
+            for fn, args in (("amvpt_temporal_moments", planes + [vp]), ("amvpt_temporal_moments_host", planes),
+                             ("amvpt_variance", [vp, vp, vp, u32, u32, vq, vp, vp]),
+                             ("amvpt_variance_host", [vp, vp, vp, u32, u32, vq, vp]),
+                             ("amvpt_denoise_variance", [vp, u32, u32, u32, vp, vp, vq, vp, vp, vp, vp, vp]),
+                             ("amvpt_denoise_variance_host", [vp, u32, u32, u32, vp, vp, vq, vp, vp, vp, vp])):
+                getattr(L, fn).restype = ctypes.c_int
+                getattr(L, fn).argtypes = args
         _hip = L
     return _hip
 
@@ -390,6 +422,113 @@ def temporal_host(image, guides, hist_image, hist_guides, hist_count, prev_views
                                  hc.ctypes.data, _views_ptr(prev_views), ctypes.byref(params), _rect_ref(rect),
                                  ctypes.byref(q), out.ctypes.data, cnt.ctypes.data), L)
     return out, cnt
+
+
+def variance_version():
+    """AMVPT_VARIANCE_VERSION of the loaded library (include/amvpt_variance.h)."""
+    return hip_lib().amvpt_variance_version()
+
+
+def variance_default_params():
+    """amvpt_variance_default_params of the loaded library."""
+    c = hip_lib().amvpt_variance_default_params()
+    return VarianceParams(*c.values())
+
+
+def temporal_moments_device(image_ptr, channels, guides_ptr, hist_image_ptr, hist_guides_ptr, hist_count_ptr, hist_moments_ptr,
+                            prev_views, params, out_image_ptr, out_count_ptr, out_moments_ptr, tp=None, rect=None, stream=None):
+    """amvpt_temporal_moments over device pointers: temporal_device with the (H, W, 2) planes of the luminance moments,
+    hist_moments_ptr in and out_moments_ptr out."""
+    L = hip_lib()
+    q = tp if tp is not None else temporal_default_params()
+    _check(L.amvpt_temporal_moments(ctypes.c_void_p(image_ptr), channels, ctypes.c_void_p(guides_ptr),
+                                    ctypes.c_void_p(hist_image_ptr), ctypes.c_void_p(hist_guides_ptr),
+                                    ctypes.c_void_p(hist_count_ptr), ctypes.c_void_p(hist_moments_ptr), _views_ptr(prev_views),
+                                    ctypes.byref(params), _rect_ref(rect), ctypes.byref(q), ctypes.c_void_p(out_image_ptr),
+                                    ctypes.c_void_p(out_count_ptr), ctypes.c_void_p(out_moments_ptr),
+                                    ctypes.c_void_p(stream or 0)), L)
+
+
+def temporal_moments_host(image, guides, hist_image, hist_guides, hist_count, hist_moments, prev_views, params, tp=None,
+                          rect=None):
+    """amvpt_temporal_moments_host over numpy: temporal_host with the (H, W, 2) history of the luminance moments ->
+    (image, count, moments).  Image and count are temporal_host's, bit for bit."""
+    L = hip_lib()
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    g = np.ascontiguousarray(guides, dtype=np.float32)
+    hi = np.ascontiguousarray(hist_image, dtype=np.float32)
+    hg = np.ascontiguousarray(hist_guides, dtype=np.float32)
+    hc = np.ascontiguousarray(hist_count, dtype=np.float32)
+    hm = np.ascontiguousarray(hist_moments, dtype=np.float32)
+    if img.ndim != 3 or g.shape != img.shape[:2] + (8,):
+        raise ValueError("temporal_moments_host: an (H, W, C) image and (H, W, 8) guide records of its size are needed")
+    if hi.shape != img.shape or hg.shape != g.shape or hc.size != g.shape[0] * g.shape[1] or hm.shape != g.shape[:2] + (2,):
+        raise ValueError("temporal_moments_host: the history planes must have the sizes of the image, the guides, (H, W) "
+                         "and (H, W, 2)")
+    q = tp if tp is not None else temporal_default_params()
+    out, cnt, mom = np.empty_like(img), np.empty(img.shape[:2], dtype=np.float32), np.empty_like(hm)
+    _check(L.amvpt_temporal_moments_host(img.ctypes.data, img.shape[2], g.ctypes.data, hi.ctypes.data, hg.ctypes.data,
+                                         hc.ctypes.data, hm.ctypes.data, _views_ptr(prev_views), ctypes.byref(params),
+                                         _rect_ref(rect), ctypes.byref(q), out.ctypes.data, cnt.ctypes.data, mom.ctypes.data), L)
+    return out, cnt, mom
+
+
+def variance_device(moments_ptr, count_ptr, guides_ptr, width, height, out_ptr, params=None, stream=None):
+    """amvpt_variance over device pointers, ordered on `stream`: (H, W, 2) moments, (H, W) count and (H, W, 8) guide
+    records -> the (H, W) variance of the accumulated luminance at out_ptr."""
+    L = hip_lib()
+    q = params if params is not None else variance_default_params()
+    _check(L.amvpt_variance(ctypes.c_void_p(moments_ptr), ctypes.c_void_p(count_ptr), ctypes.c_void_p(guides_ptr), width,
+                            height, ctypes.byref(q), ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream or 0)), L)
+
+
+def variance_host(moments, count, guides, params=None):
+    """amvpt_variance_host over numpy: (H, W, 2) moments, (H, W) count, (H, W, 8) guide records -> (H, W) variance.
+    Bit-identical to the device entry; needs no device."""
+    L = hip_lib()
+    m = np.ascontiguousarray(moments, dtype=np.float32)
+    g = np.ascontiguousarray(guides, dtype=np.float32)
+    c = np.ascontiguousarray(count, dtype=np.float32)
+    if g.ndim != 3 or g.shape[2] != 8 or m.shape != g.shape[:2] + (2,) or c.shape != g.shape[:2]:
+        raise ValueError("variance_host: (H, W, 2) moments, an (H, W) count and (H, W, 8) guide records are needed")
+    q = params if params is not None else variance_default_params()
+    out = np.empty(g.shape[:2], dtype=np.float32)
+    _check(L.amvpt_variance_host(m.ctypes.data, c.ctypes.data, g.ctypes.data, g.shape[1], g.shape[0], ctypes.byref(q),
+                                 out.ctypes.data), L)
+    return out
+
+
+def denoise_variance_device(image_ptr, channels, width, height, variance_ptr, guides_ptr, out_ptr, scratch_ptr=None,
+                            var_out_ptr=None, var_scratch_ptr=None, params=None, stream=None):
+    """amvpt_denoise_variance over device pointers, ordered on `stream`: image, (H, W) variance and guide records ->
+    out_ptr and, where given, the filtered variance at var_out_ptr.  scratch_ptr and var_scratch_ptr may be None when
+    iterations is 1, var_out_ptr when it is at most 2."""
+    L = hip_lib()
+    q = params if params is not None else variance_default_params()
+    _check(L.amvpt_denoise_variance(ctypes.c_void_p(image_ptr), channels, width, height, ctypes.c_void_p(variance_ptr),
+                                    ctypes.c_void_p(guides_ptr), ctypes.byref(q), ctypes.c_void_p(out_ptr),
+                                    ctypes.c_void_p(scratch_ptr or 0), ctypes.c_void_p(var_out_ptr or 0),
+                                    ctypes.c_void_p(var_scratch_ptr or 0), ctypes.c_void_p(stream or 0)), L)
+
+
+def denoise_variance_host(image, variance, guides, params=None):
+    """amvpt_denoise_variance_host over numpy: (H, W, 3 or 4) image, (H, W) variance, (H, W, 8) guide records ->
+    (filtered image, filtered variance).  Bit-identical to the device entry; needs no device."""
+    L = hip_lib()
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    g = np.ascontiguousarray(guides, dtype=np.float32)
+    v = np.ascontiguousarray(variance, dtype=np.float32)
+    if img.ndim != 3 or g.shape != img.shape[:2] + (8,) or v.shape != img.shape[:2]:
+        raise ValueError("denoise_variance_host: an (H, W, C) image, an (H, W) variance and (H, W, 8) guide records of its "
+                         "size are needed")
+    q = params if params is not None else variance_default_params()
+    h, w, c = img.shape
+    out, vout = np.empty_like(img), np.empty_like(v)
+    scratch, vscratch = (np.empty_like(img), np.empty_like(v)) if q.iterations > 1 else (None, None)
+    _check(L.amvpt_denoise_variance_host(img.ctypes.data, c, w, h, v.ctypes.data, g.ctypes.data, ctypes.byref(q),
+                                         out.ctypes.data, scratch.ctypes.data if scratch is not None else None,
+                                         vout.ctypes.data, vscratch.ctypes.data if vscratch is not None else None), L)
+    return out, vout
 
 
 def guides_version():
@@ -1015,10 +1154,14 @@ class TemporalAccumulator:
     """Temporal accumulation over a sequence of frames (include/amvpt_temporal.h).  It owns two sets of the three
     planes (accumulated image, guide records, history count) as torch device tensors and the views of the last frame;
     `push` takes the current developed frame, runs amvpt_guides and amvpt_temporal on the device and swaps the sets.
-    A change of film size, channel count or n_views starts over, as `reset` does."""
+    A change of film size, channel count or n_views starts over, as `reset` does.
+    moments=True keeps a fourth plane, the two luminance moments of include/amvpt_variance.h, and accumulates through
+    amvpt_temporal_moments (image and count are the same bits either way); `variance` and `denoise` then run the
+    other two stages of that header over the accumulator's own tensors."""
 
-    def __init__(self, params=None):
+    def __init__(self, params=None, moments=False):
         self.params = params if params is not None else temporal_default_params()
+        self.with_moments = bool(moments)
         self._scene = None   # (Scene, DeviceScene) of device_scene_for
         self.reset()
 
@@ -1054,6 +1197,45 @@ class TemporalAccumulator:
         """The history count of the last push, (H, W) on the device."""
         return self._sets[self._cur][2] if self._sets and self.frames else None
 
+    @property
+    def moments(self):
+        """The luminance moments of the last push, (H, W, 2) on the device (None without moments=True)."""
+        return self._sets[self._cur][3] if self._sets and self.frames and self.with_moments else None
+
+    def _stream(self, stream):
+        import torch
+        return torch.cuda.current_stream() if not stream else torch.cuda.ExternalStream(int(stream))
+
+    def variance(self, params=None, stream=None):
+        """amvpt_variance over the planes of the last push -> the (H, W) variance of the accumulated luminance, a new
+        device tensor.  `params` is a VarianceParams (None: the defaults)."""
+        if self.moments is None:
+            raise ValueError("TemporalAccumulator.variance: needs moments=True and a pushed frame")
+        import torch
+        h, w = self.count.shape
+        st = self._stream(stream)
+        with torch.cuda.stream(st):
+            var = torch.empty((h, w), dtype=torch.float32, device="cuda")
+            variance_device(self.moments.data_ptr(), self.count.data_ptr(), self.guides.data_ptr(), w, h, var.data_ptr(),
+                            params=params, stream=st.cuda_stream)
+        return var
+
+    def denoise(self, params=None, stream=None):
+        """amvpt_variance and amvpt_denoise_variance over the planes of the last push -> (filtered image, filtered
+        variance), new device tensors; the history is not touched."""
+        import torch
+        q = params if params is not None else variance_default_params()
+        var = self.variance(q, stream=stream)
+        img = self.image
+        h, w, c = img.shape
+        st = self._stream(stream)
+        with torch.cuda.stream(st):
+            out, scratch = torch.empty_like(img), torch.empty_like(img)
+            vout, vscratch = torch.empty_like(var), torch.empty_like(var)
+            denoise_variance_device(img.data_ptr(), c, w, h, var.data_ptr(), self.guides.data_ptr(), out.data_ptr(),
+                                    scratch.data_ptr(), vout.data_ptr(), vscratch.data_ptr(), params=q, stream=st.cuda_stream)
+        return out, vout
+
     def push(self, device_scene, views, params, image, stream=None):
         """Accumulate one frame: `image` is the developed frame of `params`' film on the device, a torch tensor
         (H, W, 3 or 4) or a device pointer (then 4 channels with film_alpha, else 3); `views` the host ViewDesc table
@@ -1077,7 +1259,9 @@ class TemporalAccumulator:
                 self._key = key
                 self._sets = [(torch.zeros((h, w, c), dtype=torch.float32, device="cuda"),
                                torch.zeros((h, w, 8), dtype=torch.float32, device="cuda"),
-                               torch.zeros((h, w), dtype=torch.float32, device="cuda")) for _ in range(2)]
+                               torch.zeros((h, w), dtype=torch.float32, device="cuda")) +
+                              ((torch.zeros((h, w, 2), dtype=torch.float32, device="cuda"),) if self.with_moments else ())
+                              for _ in range(2)]
             hist = self._sets[self._cur]
             cur = self._sets[1 - self._cur]
             if self.prev_views is None:   # no history: its count is zero, any valid view table serves
@@ -1086,8 +1270,13 @@ class TemporalAccumulator:
             else:
                 prev = self.prev_views
             device_scene.guides(views, params, cur[1].data_ptr(), stream=st.cuda_stream)
-            temporal_device(ptr, c, cur[1].data_ptr(), hist[0].data_ptr(), hist[1].data_ptr(), hist[2].data_ptr(), prev,
-                            params, cur[0].data_ptr(), cur[2].data_ptr(), tp=self.params, stream=st.cuda_stream)
+            if self.with_moments:
+                temporal_moments_device(ptr, c, cur[1].data_ptr(), hist[0].data_ptr(), hist[1].data_ptr(), hist[2].data_ptr(),
+                                        hist[3].data_ptr(), prev, params, cur[0].data_ptr(), cur[2].data_ptr(),
+                                        cur[3].data_ptr(), tp=self.params, stream=st.cuda_stream)
+            else:
+                temporal_device(ptr, c, cur[1].data_ptr(), hist[0].data_ptr(), hist[1].data_ptr(), hist[2].data_ptr(), prev,
+                                params, cur[0].data_ptr(), cur[2].data_ptr(), tp=self.params, stream=st.cuda_stream)
         keep = (ViewDesc * n_views)()
         ctypes.memmove(keep, views, ctypes.sizeof(keep))
         self.prev_views = keep

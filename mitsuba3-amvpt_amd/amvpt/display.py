@@ -173,7 +173,12 @@ def display(scene, preset=None, size=(1280, 720), quilt=False, nearest=False, se
     is the cached one afterwards, so with rerender=False a frame already filtered is filtered again.
     temporal None: every frame stands alone, and the call and its bytes are what they are without the keyword.  An
     amvpt.TemporalAccumulator is applied between develop and the denoiser (_display_temporal): the frame is rendered,
-    accumulated, filtered and shown through the C-ABI's device entries, and the accumulator keeps the history."""
+    accumulated, filtered and shown through the C-ABI's device entries, and the accumulator keeps the history.
+    With an accumulator built with moments=True, denoise may be an amvpt.VarianceParams: the variance-guided filter of
+    include/amvpt_variance.h (temporal with moments -> amvpt_variance -> amvpt_denoise_variance) in the denoiser's
+    place."""
+    if isinstance(denoise, amvpt.VarianceParams) and (temporal is None or not temporal.with_moments):
+        raise ValueError("display: a VarianceParams denoiser needs temporal=TemporalAccumulator(moments=True)")
     if temporal is not None:
         return _display_temporal(scene, temporal, preset, size, quilt, nearest, sensor, seed, spp, counters, stream,
                                  rerender, denoise)
@@ -204,7 +209,8 @@ def display(scene, preset=None, size=(1280, 720), quilt=False, nearest=False, se
 def _display_temporal(scene, acc, preset, size, quilt, nearest, sensor, seed, spp, counters, stream, rerender, denoise):
     """display with a TemporalAccumulator: render -> develop -> temporal accumulation -> (denoiser) -> sRGB quilt ->
     lenticular image over torch device tensors; the display image is downloaded once (denoise=True also downloads
-    the guide records, for denoise_sigma_plane; a DenoiseParams does not).  The device scene is a second one beside
+    the guide records, for denoise_sigma_plane; a DenoiseParams does not; a VarianceParams runs the accumulator's own
+    variance and variance-guided filter instead, TemporalAccumulator.denoise).  The device scene is a second one beside
     the host library's, created once per scene and kept on the accumulator (TemporalAccumulator.device_scene_for);
     the frame the host library caches for rerender=False is not touched."""
     import torch
@@ -223,7 +229,9 @@ def _display_temporal(scene, acc, preset, size, quilt, nearest, sensor, seed, sp
         _check_hip(L.amvpt_develop(ctypes.c_void_p(film.data_ptr()), ctypes.c_void_p(img.data_ptr()), w, h, p.film_alpha,
                                    ctypes.c_void_p(st.cuda_stream)), L)
         frame = acc.push(dev, vd, p, img, stream=st.cuda_stream)
-        if denoise is not None and denoise is not False:
+        if isinstance(denoise, amvpt.VarianceParams):
+            frame, _ = acc.denoise(denoise, stream=st.cuda_stream)
+        elif denoise is not None and denoise is not False:
             q = denoise if isinstance(denoise, amvpt.DenoiseParams) else amvpt.DenoiseParams(
                 sigma_plane=amvpt.denoise_sigma_plane(acc.guides.cpu().numpy()))
             out, scratch = torch.empty_like(frame), torch.empty_like(frame)

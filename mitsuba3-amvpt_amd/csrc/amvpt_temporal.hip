@@ -4,6 +4,9 @@
  * pixel, blocks of 32 x 8 pixels in a flat grid; a pure gather with no LDS, no atomics and no device-wide
  * synchronisation.  The previous views travel to the device once per call, into a buffer the library keeps for reuse
  * (ViewBuf below).  The per-pixel function is dtemporal.h's, shared with the host-only entry below.
+ *
+ * amvpt_temporal_moments of include/amvpt_variance.h lives here too: k_temporal_moments is the second instance of that
+ * per-pixel function, and its entries share the checks, the view table's upload and the launch with amvpt_temporal's.
  */
 #include <hip/hip_runtime.h>
 
@@ -15,6 +18,7 @@
 #include <vector>
 
 #include "../../include/amvpt_temporal.h"
+#include "../../include/amvpt_variance.h"
 #include "dtemporal.h"
 #include "internal.h"
 
@@ -24,6 +28,14 @@ static constexpr int kTileW = 32, kTileH = 8;
 static constexpr uint32_t kTemporalBlock = kTileW * kTileH;
 
 __global__ void __launch_bounds__(kTemporalBlock) k_temporal(TemporalArgs A) {
+    const int x = (int) (blockIdx.x % A.tiles_x) * kTileW + (int) (threadIdx.x % kTileW);
+    const int y = (int) (blockIdx.x / A.tiles_x) * kTileH + (int) (threadIdx.x / kTileW);
+    if (x >= A.L.rw || y >= A.L.rh) return;
+    temporal_pixel(A, x, y);
+}
+
+/* amvpt_temporal_moments (include/amvpt_variance.h): the moments instance of the same per-pixel function */
+__global__ void __launch_bounds__(kTemporalBlock) k_temporal_moments(TemporalMomentsArgs A) {
     const int x = (int) (blockIdx.x % A.tiles_x) * kTileW + (int) (threadIdx.x % kTileW);
     const int y = (int) (blockIdx.x / A.tiles_x) * kTileH + (int) (threadIdx.x / kTileW);
     if (x >= A.L.rw || y >= A.L.rh) return;
@@ -183,6 +195,62 @@ static amvpt_status temporal_check(const char *who, const float *image, uint32_t
     return AMVPT_OK;
 }
 
+/* the refusals amvpt_temporal_moments adds to temporal_check's: its two planes, h x w x 2 over the same rectangle */
+static amvpt_status temporal_moments_check(const char *who, const float *image, uint32_t channels, const float *guides,
+                                           const float *hist_image, const float *hist_guides, const float *hist_count,
+                                           const float *hist_moments, const amvpt_view_desc *prev_views, const amvpt_params *p,
+                                           const uint32_t *rect, const amvpt_temporal_params *tp, float *out_image,
+                                           float *out_count, float *out_moments, TemporalMomentsArgs &A) {
+    const std::string s = std::string(who) + ": ";
+    auto bad = [&](const std::string &what) { set_error(s + what); return AMVPT_ERR_INVALID; };
+    if (!hist_moments) return bad("null hist_moments");
+    if (!out_moments) return bad("null out_moments");
+    if (amvpt_status st = temporal_check(who, image, channels, guides, hist_image, hist_guides, hist_count, prev_views, p, rect,
+                                         tp, out_image, out_count, A))
+        return st;
+    const size_t ncnt = (size_t) A.L.rw * (size_t) A.L.rh * sizeof(float), nimg = ncnt * channels, ngd = ncnt * 8, nmom = ncnt * 2;
+    const struct { const void *p; size_t n; const char *name; } in[5] = {
+        {image, nimg, "the image"}, {guides, ngd, "the guides"}, {hist_image, nimg, "hist_image"},
+        {hist_guides, ngd, "hist_guides"}, {hist_count, ncnt, "hist_count"}};
+    for (const auto &i : in)
+        if (tp_overlap(out_moments, nmom, i.p, i.n)) return bad(std::string("out_moments overlaps ") + i.name);
+    if (tp_overlap(out_image, nimg, hist_moments, nmom)) return bad("out_image overlaps hist_moments");
+    if (tp_overlap(out_count, ncnt, hist_moments, nmom)) return bad("out_count overlaps hist_moments");
+    if (tp_overlap(out_moments, nmom, hist_moments, nmom)) return bad("out_moments overlaps hist_moments");
+    if (tp_overlap(out_moments, nmom, out_image, nimg)) return bad("out_moments overlaps out_image");
+    if (tp_overlap(out_moments, nmom, out_count, ncnt)) return bad("out_moments overlaps out_count");
+    A.hist_moments = hist_moments, A.out_moments = out_moments;
+    return AMVPT_OK;
+}
+
+/* the device half of both entries: the view table's upload and the one launch of kernel `k` over checked arguments */
+template <class Args>
+static amvpt_status temporal_launch(const char *who, void (*k)(Args), Args &A, const amvpt_view_desc *prev_views, void *stream) {
+    const std::string s(who);
+    /* one launch of 32 x 8 tiles covers the rectangle: film sides are at most 2^24 */
+    const uint64_t tx = ((uint32_t) A.L.rw + (uint32_t) kTileW - 1u) / (uint32_t) kTileW;
+    const uint64_t ty = ((uint32_t) A.L.rh + (uint32_t) kTileH - 1u) / (uint32_t) kTileH;
+    if (tx * ty >= (1ull << 31)) { set_error(s + ": rect above 2^31 tiles of 32 x 8 pixels"); return AMVPT_ERR_INVALID; }
+    if (!temporal_device_ok()) { set_error(s + ": no HIP device visible"); return AMVPT_ERR_NO_DEVICE; }
+    hipStream_t st = (hipStream_t) stream;
+    const uint32_t nv = A.L.multisensor ? A.L.n_views : 1u;
+    const size_t vbytes = (size_t) nv * sizeof(amvpt_view_desc);
+    ViewBuf vb;
+    if (amvpt_status rc = view_buf_take(vbytes, vb)) return rc;
+    std::memcpy(vb.host, prev_views, vbytes);
+    hipError_t e = hipMemcpyAsync(vb.p, vb.host, vbytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        A.views = (const amvpt_view_desc *) vb.p;
+        A.tiles_x = (uint32_t) tx;
+        hipLaunchKernelGGL(k, dim3((uint32_t) (tx * ty)), dim3(kTemporalBlock), 0, st, A);
+        e = hipGetLastError();
+    }
+    const hipError_t eg = view_buf_give(vb, st);
+    if (e != hipSuccess) return hip_fail((s + " launch").c_str(), (int) e);
+    if (eg != hipSuccess) return hip_fail((s + " hipEventRecord").c_str(), (int) eg);
+    return AMVPT_OK;
+}
+
 } // namespace amvpt
 
 using namespace amvpt;
@@ -222,28 +290,38 @@ amvpt_status amvpt_temporal(const float *image_device, uint32_t channels, const 
                                         hist_guides_device, hist_count_device, prev_views, params, rect, tp,
                                         out_image_device, out_count_device, A))
         return s;
-    /* one launch of 32 x 8 tiles covers the rectangle: film sides are at most 2^24 */
-    const uint64_t tx = ((uint32_t) A.L.rw + (uint32_t) kTileW - 1u) / (uint32_t) kTileW;
-    const uint64_t ty = ((uint32_t) A.L.rh + (uint32_t) kTileH - 1u) / (uint32_t) kTileH;
-    if (tx * ty >= (1ull << 31)) { set_error("amvpt_temporal: rect above 2^31 tiles of 32 x 8 pixels"); return AMVPT_ERR_INVALID; }
-    if (!temporal_device_ok()) { set_error("amvpt_temporal: no HIP device visible"); return AMVPT_ERR_NO_DEVICE; }
-    hipStream_t st = (hipStream_t) stream;
-    const uint32_t nv = A.L.multisensor ? A.L.n_views : 1u;
-    const size_t vbytes = (size_t) nv * sizeof(amvpt_view_desc);
-    ViewBuf vb;
-    if (amvpt_status s = view_buf_take(vbytes, vb)) return s;
-    std::memcpy(vb.host, prev_views, vbytes);
-    hipError_t e = hipMemcpyAsync(vb.p, vb.host, vbytes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-        A.views = (const amvpt_view_desc *) vb.p;
-        A.tiles_x = (uint32_t) tx;
-        hipLaunchKernelGGL(k_temporal, dim3((uint32_t) (tx * ty)), dim3(kTemporalBlock), 0, st, A);
-        e = hipGetLastError();
-    }
-    const hipError_t eg = view_buf_give(vb, st);
-    if (e != hipSuccess) return hip_fail("amvpt_temporal launch", (int) e);
-    if (eg != hipSuccess) return hip_fail("amvpt_temporal hipEventRecord", (int) eg);
+    return temporal_launch("amvpt_temporal", k_temporal, A, prev_views, stream);
+}
+
+/* include/amvpt_variance.h, stage 1 */
+amvpt_status amvpt_temporal_moments_host(const float *image, uint32_t channels, const float *guides, const float *hist_image,
+                                         const float *hist_guides, const float *hist_count, const float *hist_moments,
+                                         const amvpt_view_desc *prev_views, const amvpt_params *params, const uint32_t rect[4],
+                                         const amvpt_temporal_params *tp, float *out_image, float *out_count,
+                                         float *out_moments) {
+    TemporalMomentsArgs A;
+    if (amvpt_status s = temporal_moments_check("amvpt_temporal_moments_host", image, channels, guides, hist_image, hist_guides,
+                                                hist_count, hist_moments, prev_views, params, rect, tp, out_image, out_count,
+                                                out_moments, A))
+        return s;
+    for (int32_t y = 0; y < A.L.rh; ++y)
+        for (int32_t x = 0; x < A.L.rw; ++x) temporal_pixel(A, x, y);
     return AMVPT_OK;
+}
+
+amvpt_status amvpt_temporal_moments(const float *image_device, uint32_t channels, const float *guides_device,
+                                    const float *hist_image_device, const float *hist_guides_device,
+                                    const float *hist_count_device, const float *hist_moments_device,
+                                    const amvpt_view_desc *prev_views, const amvpt_params *params, const uint32_t rect[4],
+                                    const amvpt_temporal_params *tp, float *out_image_device, float *out_count_device,
+                                    float *out_moments_device, void *stream) {
+    TemporalMomentsArgs A;
+    if (amvpt_status s = temporal_moments_check("amvpt_temporal_moments", image_device, channels, guides_device,
+                                                hist_image_device, hist_guides_device, hist_count_device, hist_moments_device,
+                                                prev_views, params, rect, tp, out_image_device, out_count_device,
+                                                out_moments_device, A))
+        return s;
+    return temporal_launch("amvpt_temporal_moments", k_temporal_moments, A, prev_views, stream);
 }
 
 } // extern "C"

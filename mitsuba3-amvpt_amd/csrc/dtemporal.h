@@ -8,6 +8,11 @@
  *
  * A tap fetches its fields in the order of the stops: the guide record (two 16-byte halves), then the count, then
  * the colour -- a tap stopped by its view or shape fetches neither count nor colour.
+ *
+ * The function has two instances, chosen by the type of its arguments: TemporalArgs is amvpt_temporal, and
+ * TemporalMomentsArgs is amvpt_temporal_moments (include/amvpt_variance.h), which carries the two luminance moments
+ * through the same accepted taps and fetches a tap's moments last, once every stop has passed.  Everything the
+ * moments add sits behind `if constexpr`, so the first instance compiles to what it was without them.
  */
 #pragma once
 #include <hip/hip_runtime.h>
@@ -37,6 +42,14 @@ struct TemporalArgs {
     float max_history, plane_tol, normal_cos;
     uint32_t tiles_x;               /* blocks per row of the launch */
 };
+
+/* amvpt_temporal_moments: the same, with the h x w x 2 planes of the luminance moments */
+struct TemporalMomentsArgs : TemporalArgs {
+    const float *hist_moments;
+    float *out_moments;
+};
+template <class Args> struct tp_moments { static constexpr bool value = false; };
+template <> struct tp_moments<TemporalMomentsArgs> { static constexpr bool value = true; };
 
 THD bool tp_finite(float f) {
     uint32_t u;
@@ -126,8 +139,10 @@ THD void tp_tile(const TemporalLayout &L, uint32_t v, int32_t &tx0, int32_t &ty0
     tx0 = (int32_t) col * L.tw, ty0 = (int32_t) row * L.th;
 }
 
-/* the history of a hit pixel: the four taps around its reprojection; n_prev = 0 when nothing is accepted */
-THD float tp_gather(const TemporalArgs &A, const float *g, float h[3]) {
+/* the history of a hit pixel: the four taps around its reprojection; n_prev = 0 when nothing is accepted.  hm: the
+ * history of the moments (the moments instance alone) */
+template <class Args> THD float tp_gather(const Args &A, const float *g, float h[3], float hm[2]) {
+    constexpr bool kMoments = tp_moments<Args>::value;
     const TemporalLayout &L = A.L;
     const uint32_t nv = L.multisensor ? L.n_views : 1u;
     if (!(g[7] >= 0.f && g[7] < (float) nv)) return 0.f;
@@ -145,6 +160,7 @@ THD float tp_gather(const TemporalArgs &A, const float *g, float h[3]) {
     const float ax = sx - (float) x0, ay = sy - (float) y0;
     float sw = 0.f, sn = 0.f, sc[3] = {0.f, 0.f, 0.f};
     float n_lo = __builtin_huge_valf(), n_hi = 0.f;   /* the range of the accepted counts */
+    float sm[2] = {0.f, 0.f};
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int32_t qy = y0 + j;
@@ -172,19 +188,26 @@ THD float tp_gather(const TemporalArgs &A, const float *g, float h[3]) {
             sc[1] = sc[1] + w * col[1];
             sc[2] = sc[2] + w * col[2];
             sn = sn + w * cnt;
+            if constexpr (kMoments) {
+                const float *mq = A.hist_moments + 2 * at;
+                sm[0] = sm[0] + w * mq[0];
+                sm[1] = sm[1] + w * mq[1];
+            }
             n_lo = cnt < n_lo ? cnt : n_lo;
             n_hi = cnt > n_hi ? cnt : n_hi;
         }
     }
     if (!(sw > 0.f)) return 0.f;
     h[0] = sc[0] / sw, h[1] = sc[1] / sw, h[2] = sc[2] / sw;
+    if constexpr (kMoments) hm[0] = sm[0] / sw, hm[1] = sm[1] / sw;
     /* a weighted mean lies in the range of its terms; rounding alone can take the quotient out of it */
     const float n = sn / sw;
     return n < n_lo ? n_lo : (n > n_hi ? n_hi : n);
 }
 
-/* pixel (lx, ly) of the rectangle: both outputs */
-THD void temporal_pixel(const TemporalArgs &A, int32_t lx, int32_t ly) {
+/* pixel (lx, ly) of the rectangle: both outputs, and with the moments instance the third */
+template <class Args> THD void temporal_pixel(const Args &A, int32_t lx, int32_t ly) {
+    constexpr bool kMoments = tp_moments<Args>::value;
     const size_t at = (size_t) ly * (size_t) A.L.rw + (size_t) lx;
     const float *cp = A.image + A.channels * at;
     const float c[3] = {cp[0], cp[1], cp[2]};
@@ -193,7 +216,13 @@ THD void temporal_pixel(const TemporalArgs &A, int32_t lx, int32_t ly) {
     if (!tp_finite3(c)) {
         o[0] = c[0], o[1] = c[1], o[2] = c[2];
         A.out_count[at] = 0.f;
+        if constexpr (kMoments) A.out_moments[2 * at] = 0.f, A.out_moments[2 * at + 1] = 0.f;
         return;
+    }
+    float m[2] = {0.f, 0.f}, hm[2] = {0.f, 0.f};
+    if constexpr (kMoments) {
+        const float l = (0.2126f * c[0] + 0.7152f * c[1]) + 0.0722f * c[2];
+        m[0] = l, m[1] = l * l;
     }
     const float *r = A.guides + 8 * at;
     const float g[8] = {r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7]};
@@ -205,11 +234,14 @@ THD void temporal_pixel(const TemporalArgs &A, int32_t lx, int32_t ly) {
             if (cnt >= 1.f) {
                 const float *hc = A.hist_image + A.channels * at;
                 const float col[3] = {hc[0], hc[1], hc[2]};
-                if (tp_finite3(col)) h[0] = col[0], h[1] = col[1], h[2] = col[2], n_prev = cnt;
+                if (tp_finite3(col)) {
+                    h[0] = col[0], h[1] = col[1], h[2] = col[2], n_prev = cnt;
+                    if constexpr (kMoments) hm[0] = A.hist_moments[2 * at], hm[1] = A.hist_moments[2 * at + 1];
+                }
             }
         }
     } else {
-        n_prev = tp_gather(A, g, h);
+        n_prev = tp_gather(A, g, h, hm);
     }
     if (n_prev > 0.f) {
         float n = n_prev + 1.f;
@@ -219,9 +251,14 @@ THD void temporal_pixel(const TemporalArgs &A, int32_t lx, int32_t ly) {
         o[1] = h[1] + a * (c[1] - h[1]);
         o[2] = h[2] + a * (c[2] - h[2]);
         A.out_count[at] = n;
+        if constexpr (kMoments) {
+            A.out_moments[2 * at] = hm[0] + a * (m[0] - hm[0]);
+            A.out_moments[2 * at + 1] = hm[1] + a * (m[1] - hm[1]);
+        }
     } else {
         o[0] = c[0], o[1] = c[1], o[2] = c[2];
         A.out_count[at] = 1.f;
+        if constexpr (kMoments) A.out_moments[2 * at] = m[0], A.out_moments[2 * at + 1] = m[1];
     }
 }
 

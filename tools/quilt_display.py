@@ -3,7 +3,7 @@
 
     python tools/quilt_display.py [scene.xml] [-D key=value ...] [--preset NAME --presets presets.csv]
                                   [--size W H] [--nearest] [--out-dir DIR] [--depth PATH]
-                                  [--denoise [ITER]] [--temporal N]
+                                  [--denoise [ITER]] [--temporal N [--denoise-variance]]
 
 Without arguments: scenes/cbox_grid.xml at a small resolution, the default preset (LKG4x8) with the scene's view
 grid, a 1280 x 720 display, written to out/<scene>_quilt.png and out/<scene>_display.png.  The frame is rendered once;
@@ -11,7 +11,9 @@ both images come from that frame.  --depth PATH also writes the depth quilt (nea
 the frame's own depth range) as an 8-bit PNG: the RGB-D companion of the quilt.  --denoise [ITER] filters the developed
 frame on the device before both images are made (amvpt.denoise's defaults; ITER iterations instead of 3).  --temporal N
 renders N frames at the given spp with consecutive seeds through an amvpt.TemporalAccumulator and shows the last one
-(with --denoise, filtered after the accumulation).
+(with --denoise, filtered after the accumulation).  --temporal N --denoise-variance filters with the variance-guided
+denoiser of include/amvpt_variance.h instead: the accumulator carries the luminance moments, and the filter is as wide as
+the variance they give (amvpt.VarianceParams' defaults, sigma_plane scaled to the scene).
 """
 import argparse
 import os
@@ -37,7 +39,11 @@ def main():
                     help="filter the frame with the a-trous denoiser (amvpt.denoise), ITER iterations (default 3)")
     ap.add_argument("--temporal", type=int, default=None, metavar="N",
                     help="accumulate N frames of consecutive seeds (amvpt.TemporalAccumulator) and show the last")
+    ap.add_argument("--denoise-variance", action="store_true",
+                    help="with --temporal: filter with the variance-guided denoiser (amvpt.VarianceParams' defaults)")
     a = ap.parse_args()
+    if a.denoise_variance and (a.temporal is None or a.denoise is not None):
+        ap.error("--denoise-variance needs --temporal and excludes --denoise")
 
     import amvpt
     import amvpt.display as D
@@ -84,8 +90,10 @@ def temporal_frames(a, ap, scene, preset, cnt):
     import amvpt.display as D
     if a.temporal < 1:
         ap.error("--temporal needs at least one frame")
-    acc = amvpt.TemporalAccumulator()
+    acc = amvpt.TemporalAccumulator(moments=a.denoise_variance)
     denoise = amvpt.denoise_params_for(scene, iterations=a.denoise) if a.denoise is not None else None
+    if a.denoise_variance:
+        denoise = amvpt.VarianceParams(sigma_plane=amvpt.denoise_params_for(scene).sigma_plane)
     for i in range(a.temporal):
         image = D.display(scene, preset, size=tuple(a.size), nearest=a.nearest, seed=a.seed + i, spp=a.spp, counters=cnt,
                           denoise=denoise, temporal=acc)
