@@ -161,6 +161,21 @@ class VarianceParams(ctypes.Structure):
                 "min_history=%r)" % self.values())
 
 
+class SynthParams(ctypes.Structure):
+    """amvpt_synth_params (include/amvpt_synth.h).  Without arguments: amvpt_synth_default_params' values,
+    {0.02, 0.9, 1e5, 4}; plane_tol is in world units."""
+    _fields_ = [("plane_tol", f32), ("normal_cos", f32), ("view_falloff", f32), ("fill_iterations", u32)]
+
+    def __init__(self, plane_tol=0.02, normal_cos=0.9, view_falloff=1e5, fill_iterations=4):
+        super().__init__(plane_tol, normal_cos, view_falloff, fill_iterations)
+
+    def values(self):
+        return (self.plane_tol, self.normal_cos, self.view_falloff, self.fill_iterations)
+
+    def __repr__(self):
+        return "SynthParams(plane_tol=%r, normal_cos=%r, view_falloff=%r, fill_iterations=%r)" % self.values()
+
+
 # amvpt_run_exchange_fn: (ctx, n_runs, *run_lane_begin, *run_count, *run_prefix, *total) -> 0 on success
 RunExchangeFn = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, u32, ctypes.POINTER(u64), ctypes.POINTER(u64),
                                  ctypes.POINTER(u64), ctypes.POINTER(u64))
@@ -315,6 +330,18 @@ def hip_lib():
                              ("amvpt_variance_host", [vp, vp, vp, u32, u32, vq, vp]),
                              ("amvpt_denoise_variance", [vp, u32, u32, u32, vp, vp, vq, vp, vp, vp, vp, vp]),
                              ("amvpt_denoise_variance_host", [vp, u32, u32, u32, vp, vp, vq, vp, vp, vp, vp])):
+                getattr(L, fn).restype = ctypes.c_int
+                getattr(L, fn).argtypes = args
+        if hasattr(L, "amvpt_synth_version"):   # include/amvpt_synth.h
+            vp = ctypes.c_void_p
+            sq = ctypes.POINTER(SynthParams)
+            L.amvpt_synth_version.restype = u32
+            L.amvpt_synth_default_params.restype = SynthParams
+            L.amvpt_synth_default_params.argtypes = []
+            planes = [vp, u32, vp, vp, ctypes.POINTER(Params), vp, vp, ctypes.POINTER(Params), ctypes.POINTER(u32 * 4), sq, vp, vp]
+            fill = [vp, u32, u32, u32, vp, vp, sq, vp, vp, vp, vp]
+            for fn, args in (("amvpt_synth", planes + [vp]), ("amvpt_synth_host", planes),
+                             ("amvpt_synth_fill", fill + [vp]), ("amvpt_synth_fill_host", fill)):
                 getattr(L, fn).restype = ctypes.c_int
                 getattr(L, fn).argtypes = args
         _hip = L
@@ -529,6 +556,85 @@ def denoise_variance_host(image, variance, guides, params=None):
                                          out.ctypes.data, scratch.ctypes.data if scratch is not None else None,
                                          vout.ctypes.data, vscratch.ctypes.data if vscratch is not None else None), L)
     return out, vout
+
+
+def synth_version():
+    """AMVPT_SYNTH_VERSION of the loaded library (include/amvpt_synth.h)."""
+    return hip_lib().amvpt_synth_version()
+
+
+def synth_default_params():
+    """amvpt_synth_default_params of the loaded library."""
+    c = hip_lib().amvpt_synth_default_params()
+    return SynthParams(*c.values())
+
+
+def synth_device(src_image_ptr, channels, src_guides_ptr, src_views, src_params, dst_guides_ptr, dst_views, dst_params,
+                 dst_image_ptr, dst_cover_ptr, sp=None, rect=None, stream=None):
+    """amvpt_synth over device pointers, ordered on `stream`: the source quilt (image, guide records, the host ViewDesc
+    table and the Params of its layout) and the target quilt's guide records, views and Params -> dst_image_ptr,
+    dst_cover_ptr.  `rect` = (x0, y0, w, h), whole tiles of the target quilt that the target planes hold alone (None: all
+    of it)."""
+    L = hip_lib()
+    q = sp if sp is not None else synth_default_params()
+    _check(L.amvpt_synth(ctypes.c_void_p(src_image_ptr), channels, ctypes.c_void_p(src_guides_ptr), _views_ptr(src_views),
+                         ctypes.byref(src_params), ctypes.c_void_p(dst_guides_ptr), _views_ptr(dst_views),
+                         ctypes.byref(dst_params), _rect_ref(rect), ctypes.byref(q), ctypes.c_void_p(dst_image_ptr),
+                         ctypes.c_void_p(dst_cover_ptr), ctypes.c_void_p(stream or 0)), L)
+
+
+def synth_host(src_image, src_guides, src_views, src_params, dst_guides, dst_views, dst_params, sp=None, rect=None):
+    """amvpt_synth_host over numpy: the (Hs, Ws, 3 or 4) float32 source image, its (Hs, Ws, 8) guide records, views and
+    Params, and the target's (h, w, 8) guide records, views and Params -> (image (h, w, C), cover (h, w)).
+    Bit-identical to the device entry; needs no device."""
+    L = hip_lib()
+    img = np.ascontiguousarray(src_image, dtype=np.float32)
+    sg = np.ascontiguousarray(src_guides, dtype=np.float32)
+    dg = np.ascontiguousarray(dst_guides, dtype=np.float32)
+    if img.ndim != 3 or sg.shape != img.shape[:2] + (8,):
+        raise ValueError("synth_host: an (Hs, Ws, C) source image and (Hs, Ws, 8) guide records of its size are needed")
+    if img.shape[:2] != (int(src_params.film_height), int(src_params.film_width)):
+        raise ValueError("synth_host: the source planes must hold the whole film of src_params")
+    want = (int(rect[3]), int(rect[2])) if rect is not None else (int(dst_params.film_height), int(dst_params.film_width))
+    if dg.ndim != 3 or dg.shape != want + (8,):
+        raise ValueError("synth_host: (h, w, 8) target guide records of the rectangle (or of dst_params' film) are needed")
+    q = sp if sp is not None else synth_default_params()
+    out, cover = np.empty(dg.shape[:2] + (img.shape[2],), dtype=np.float32), np.empty(dg.shape[:2], dtype=np.float32)
+    _check(L.amvpt_synth_host(img.ctypes.data, img.shape[2], sg.ctypes.data, _views_ptr(src_views), ctypes.byref(src_params),
+                              dg.ctypes.data, _views_ptr(dst_views), ctypes.byref(dst_params), _rect_ref(rect),
+                              ctypes.byref(q), out.ctypes.data, cover.ctypes.data), L)
+    return out, cover
+
+
+def synth_fill_device(image_ptr, channels, width, height, cover_ptr, guides_ptr, out_ptr, cover_out_ptr, scratch_ptr=None,
+                      cover_scratch_ptr=None, sp=None, stream=None):
+    """amvpt_synth_fill over device pointers, ordered on `stream`: sp.fill_iterations iterations of the hole fill ->
+    out_ptr, cover_out_ptr.  scratch_ptr and cover_scratch_ptr may be None when fill_iterations is at most 1."""
+    L = hip_lib()
+    q = sp if sp is not None else synth_default_params()
+    _check(L.amvpt_synth_fill(ctypes.c_void_p(image_ptr), channels, width, height, ctypes.c_void_p(cover_ptr),
+                              ctypes.c_void_p(guides_ptr), ctypes.byref(q), ctypes.c_void_p(out_ptr),
+                              ctypes.c_void_p(scratch_ptr or 0), ctypes.c_void_p(cover_out_ptr),
+                              ctypes.c_void_p(cover_scratch_ptr or 0), ctypes.c_void_p(stream or 0)), L)
+
+
+def synth_fill_host(image, cover, guides, sp=None):
+    """amvpt_synth_fill_host over numpy: (H, W, 3 or 4) image, (H, W) cover, (H, W, 8) guide records -> (image, cover)
+    after sp.fill_iterations iterations.  Bit-identical to the device entry; needs no device."""
+    L = hip_lib()
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    g = np.ascontiguousarray(guides, dtype=np.float32)
+    c = np.ascontiguousarray(cover, dtype=np.float32)
+    if img.ndim != 3 or g.shape != img.shape[:2] + (8,) or c.shape != img.shape[:2]:
+        raise ValueError("synth_fill_host: an (H, W, C) image, an (H, W) cover and (H, W, 8) guide records of its size are needed")
+    q = sp if sp is not None else synth_default_params()
+    h, w, ch = img.shape
+    out, cout = np.empty_like(img), np.empty_like(c)
+    scratch, cscratch = (np.empty_like(img), np.empty_like(c)) if q.fill_iterations > 1 else (None, None)
+    _check(L.amvpt_synth_fill_host(img.ctypes.data, ch, w, h, c.ctypes.data, g.ctypes.data, ctypes.byref(q), out.ctypes.data,
+                                   scratch.ctypes.data if scratch is not None else None, cout.ctypes.data,
+                                   cscratch.ctypes.data if cscratch is not None else None), L)
+    return out, cout
 
 
 def guides_version():
@@ -1283,3 +1389,79 @@ class TemporalAccumulator:
         self._cur = 1 - self._cur
         self.frames += 1
         return cur[0]
+
+
+class ViewSynthesizer:
+    """View synthesis into the dense quilt of `dst_scene` (include/amvpt_synth.h): a host Scene of the same XML as the
+    rendered one, loaded with the dense grid.  It keeps the target views, the target Params and, as a torch device
+    tensor, the target guide records, computed with DeviceScene.guides at the first `run` and again only when the bytes
+    of the target views change (`guide_runs` counts).  `holes` is the number of pixels whose cover is 0 after the last
+    run, whose planes stay reachable as `source_image`, `source_guides`, `image` and `cover`."""
+
+    def __init__(self, dst_scene, params=None, sensor=0):
+        self.params = params if params is not None else synth_default_params()
+        self.scene, self.sensor = dst_scene, sensor
+        self.guides = None
+        self.guide_runs = 0
+        self._guides_key = None
+        self.holes = None
+        self.source_image = self.source_guides = self.image = self.cover = None   # the planes of the last run
+        self._device = None   # (Scene, DeviceScene) of device_scene_for
+        self.set_views(*dst_scene.describe(sensor, 0, 0)[1:])
+
+    def set_views(self, views, params):
+        """The target views (a host ViewDesc table) and the Params of the target quilt; copies are kept."""
+        self.dst_params = Params.from_buffer_copy(params)
+        n = max(1, int(params.n_views)) if params.multisensor else 1
+        keep = (ViewDesc * n)()
+        ctypes.memmove(keep, views, ctypes.sizeof(keep))
+        self.dst_views = keep
+
+    def device_scene_for(self, scene, scene_desc):
+        """The DeviceScene this synthesizer keeps for the loaded `scene` (amvpt.display.display(..., synth=) without an
+        accumulator): created from `scene_desc` at the first call, replaced by another scene's."""
+        if self._device is None or self._device[0] is not scene:
+            self._device = (scene, DeviceScene(scene_desc))
+        return self._device[1]
+
+    def run(self, device_scene, src_views, src_params, src_image, src_guides=None, stream=None):
+        """Synthesize the target quilt from the developed source quilt `src_image`, a contiguous float32 (Hs, Ws, 3 or
+        4) torch device tensor rendered with `src_views` / `src_params`; `src_guides` its (Hs, Ws, 8) guide records
+        (None: computed here with device_scene.guides).  Stage 1, then params.fill_iterations of stage 2, ordered on
+        `stream` (a hipStream_t handle; None: torch's current stream) -> (image (h, w, C), cover (h, w)), new tensors."""
+        import torch
+        hs, ws = int(src_params.film_height), int(src_params.film_width)
+        if (not hasattr(src_image, "data_ptr") or src_image.dtype != torch.float32 or not src_image.is_contiguous()
+                or src_image.dim() != 3 or tuple(src_image.shape[:2]) != (hs, ws)):
+            raise ValueError("ViewSynthesizer.run: a contiguous float32 (%d, %d, C) tensor is needed" % (hs, ws))
+        c = int(src_image.shape[2])
+        p = self.dst_params
+        h, w = int(p.film_height), int(p.film_width)
+        st = torch.cuda.current_stream() if not stream else torch.cuda.ExternalStream(int(stream))
+        with torch.cuda.stream(st):
+            key = bytes(self.dst_views) + bytes(p)
+            if self.guides is None or key != self._guides_key:
+                self.guides = torch.empty((h, w, 8), dtype=torch.float32, device="cuda")
+                device_scene.guides(self.dst_views, p, self.guides.data_ptr(), stream=st.cuda_stream)
+                self._guides_key = key
+                self.guide_runs += 1
+            if src_guides is None:
+                src_guides = torch.empty((hs, ws, 8), dtype=torch.float32, device="cuda")
+                device_scene.guides(src_views, src_params, src_guides.data_ptr(), stream=st.cuda_stream)
+            elif tuple(src_guides.shape) != (hs, ws, 8) or src_guides.dtype != torch.float32 or not src_guides.is_contiguous():
+                raise ValueError("ViewSynthesizer.run: src_guides must be a contiguous float32 (%d, %d, 8) tensor" % (hs, ws))
+            img = torch.empty((h, w, c), dtype=torch.float32, device="cuda")
+            cover = torch.empty((h, w), dtype=torch.float32, device="cuda")
+            synth_device(src_image.data_ptr(), c, src_guides.data_ptr(), src_views, src_params, self.guides.data_ptr(),
+                         self.dst_views, p, img.data_ptr(), cover.data_ptr(), sp=self.params, stream=st.cuda_stream)
+            if self.params.fill_iterations:
+                out, cout = torch.empty_like(img), torch.empty_like(cover)
+                many = self.params.fill_iterations > 1
+                scratch, cscratch = (torch.empty_like(img), torch.empty_like(cover)) if many else (None, None)
+                synth_fill_device(img.data_ptr(), c, w, h, cover.data_ptr(), self.guides.data_ptr(), out.data_ptr(),
+                                  cout.data_ptr(), scratch.data_ptr() if many else None, cscratch.data_ptr() if many else None,
+                                  sp=self.params, stream=st.cuda_stream)
+                img, cover = out, cout
+            self.holes = int((cover == 0).sum().item())
+        self.source_image, self.source_guides, self.image, self.cover = src_image, src_guides, img, cover
+        return img, cover

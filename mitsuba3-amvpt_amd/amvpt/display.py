@@ -163,7 +163,7 @@ def preset_for_scene(scene, sensor=0):
 
 
 def display(scene, preset=None, size=(1280, 720), quilt=False, nearest=False, sensor=0, seed=0, spp=0,
-            counters=None, stream=None, rerender=True, denoise=None, temporal=None):
+            counters=None, stream=None, rerender=True, denoise=None, temporal=None, synth=None):
     """Render `scene` and run the display stage on the device (amvpt_host_display): render -> develop -> sRGB
     quilt -> lenticular image, one download -> (size[1], size[0], 3) uint8.  preset None: preset_for_scene.
     rerender=False runs the stage alone on the developed frame the last render / display of this sensor left on
@@ -176,9 +176,16 @@ def display(scene, preset=None, size=(1280, 720), quilt=False, nearest=False, se
     accumulated, filtered and shown through the C-ABI's device entries, and the accumulator keeps the history.
     With an accumulator built with moments=True, denoise may be an amvpt.VarianceParams: the variance-guided filter of
     include/amvpt_variance.h (temporal with moments -> amvpt_variance -> amvpt_denoise_variance) in the denoiser's
-    place."""
+    place.
+    synth None: the rendered quilt is the one shown, and the call and its bytes are what they are without the keyword.
+    An amvpt.ViewSynthesizer makes the dense quilt of its own scene from the rendered one (include/amvpt_synth.h) after
+    the accumulator and the denoiser (_display_synth): render -> develop -> (temporal) -> (denoise) -> synthesis -> sRGB
+    quilt -> lenticular image, and preset None is preset_for_scene of the synthesizer's scene."""
     if isinstance(denoise, amvpt.VarianceParams) and (temporal is None or not temporal.with_moments):
         raise ValueError("display: a VarianceParams denoiser needs temporal=TemporalAccumulator(moments=True)")
+    if synth is not None:
+        return _display_synth(scene, synth, temporal, preset, size, quilt, nearest, sensor, seed, spp, counters, stream,
+                              rerender, denoise)
     if temporal is not None:
         return _display_temporal(scene, temporal, preset, size, quilt, nearest, sensor, seed, spp, counters, stream,
                                  rerender, denoise)
@@ -244,6 +251,51 @@ def _display_temporal(scene, acc, preset, size, quilt, nearest, sensor, seed, sp
         shown = torch.empty((max(dh, 0), max(dw, 0), 3), dtype=torch.uint8, device="cuda")
         interlace_device(q8.data_ptr(), w, h, 3, shown.data_ptr(), (dw, dh), preset if preset is not None else
                          preset_for_scene(scene, sensor), quilt=quilt, nearest=nearest, stream=st.cuda_stream)
+        st.synchronize()
+        return shown.cpu().numpy()
+
+
+def _display_synth(scene, synth, acc, preset, size, quilt, nearest, sensor, seed, spp, counters, stream, rerender, denoise):
+    """display with a ViewSynthesizer, with or without a TemporalAccumulator: _display_temporal's chain over torch
+    device tensors with the synthesis between the denoiser and the sRGB quilt; what is shown is the synthesizer's dense
+    quilt.  The device scene is the accumulator's where there is one, else one the synthesizer keeps."""
+    import torch
+    if not rerender:
+        raise ValueError("display: view synthesis needs a fresh frame (rerender=True)")
+    L, _ = _libs()
+    sd, vd, p = scene.describe(sensor, seed, spp)
+    dev = acc.device_scene_for(scene, sd) if acc is not None else synth.device_scene_for(scene, sd)
+    h, w = int(p.film_height), int(p.film_width)
+    c = 4 if p.film_alpha else 3
+    st = torch.cuda.current_stream() if not stream else torch.cuda.ExternalStream(int(stream))
+    with torch.cuda.stream(st):
+        film = torch.zeros((h, w, c + 1), dtype=torch.float32, device="cuda")
+        img = torch.empty((h, w, c), dtype=torch.float32, device="cuda")
+        dev.render(vd, p, film.data_ptr(), stream=st.cuda_stream, counters=counters)
+        _check_hip(L.amvpt_develop(ctypes.c_void_p(film.data_ptr()), ctypes.c_void_p(img.data_ptr()), w, h, p.film_alpha,
+                                   ctypes.c_void_p(st.cuda_stream)), L)
+        if acc is not None:
+            frame, guides = acc.push(dev, vd, p, img, stream=st.cuda_stream), acc.guides
+        else:
+            frame, guides = img, torch.empty((h, w, 8), dtype=torch.float32, device="cuda")
+            dev.guides(vd, p, guides.data_ptr(), stream=st.cuda_stream)
+        if isinstance(denoise, amvpt.VarianceParams):
+            frame, _ = acc.denoise(denoise, stream=st.cuda_stream)
+        elif denoise is not None and denoise is not False:
+            q = denoise if isinstance(denoise, amvpt.DenoiseParams) else amvpt.DenoiseParams(
+                sigma_plane=amvpt.denoise_sigma_plane(guides.cpu().numpy()))
+            out, scratch = torch.empty_like(frame), torch.empty_like(frame)
+            amvpt.denoise_device(frame.data_ptr(), c, w, h, guides.data_ptr(), out.data_ptr(), scratch.data_ptr(), q,
+                                 stream=st.cuda_stream)
+            frame = out
+        dense, _ = synth.run(dev, vd, p, frame, guides, stream=st.cuda_stream)
+        qh, qw = int(dense.shape[0]), int(dense.shape[1])
+        q8 = torch.empty((qh, qw, 3), dtype=torch.uint8, device="cuda")
+        srgb8_device(dense.data_ptr(), c, qw, qh, q8.data_ptr(), stream=st.cuda_stream)
+        dw, dh = int(size[0]), int(size[1])
+        shown = torch.empty((max(dh, 0), max(dw, 0), 3), dtype=torch.uint8, device="cuda")
+        interlace_device(q8.data_ptr(), qw, qh, 3, shown.data_ptr(), (dw, dh), preset if preset is not None else
+                         preset_for_scene(synth.scene, synth.sensor), quilt=quilt, nearest=nearest, stream=st.cuda_stream)
         st.synchronize()
         return shown.cpu().numpy()
 

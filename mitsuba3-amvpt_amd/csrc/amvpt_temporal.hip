@@ -3,7 +3,7 @@
  * through the guide records and blended with the current one.  One launch on the caller's stream, one thread per
  * pixel, blocks of 32 x 8 pixels in a flat grid; a pure gather with no LDS, no atomics and no device-wide
  * synchronisation.  The previous views travel to the device once per call, into a buffer the library keeps for reuse
- * (ViewBuf below).  The per-pixel function is dtemporal.h's, shared with the host-only entry below.
+ * (ViewBuf of viewbuf.h).  The per-pixel function is dtemporal.h's, shared with the host-only entry below.
  *
  * amvpt_temporal_moments of include/amvpt_variance.h lives here too: k_temporal_moments is the second instance of that
  * per-pixel function, and its entries share the checks, the view table's upload and the launch with amvpt_temporal's.
@@ -13,7 +13,6 @@
 #include <atomic>
 #include <cstdint>
 #include <cstring>
-#include <mutex>
 #include <string>
 #include <vector>
 
@@ -21,6 +20,7 @@
 #include "../../include/amvpt_variance.h"
 #include "dtemporal.h"
 #include "internal.h"
+#include "viewbuf.h"
 
 namespace amvpt {
 
@@ -50,67 +50,6 @@ static bool temporal_device_ok() {
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return false;
     seen.store(true, std::memory_order_relaxed);
     return true;
-}
-
-/*
- * The uploads of the view table.  A ViewBuf is a device buffer with a pinned host block of the same size.  A call
- * takes a kept ViewBuf of its device that is large enough and whose last use has finished (the event behind that
- * launch, polled: nobody waits), or allocates one; it copies the caller's table into the pinned block before it
- * returns, so the caller's memory, pageable or pinned, is free again and the copy to the device is asynchronous;
- * it records the event behind its own launch and gives the ViewBuf back.  Calls on several streams never share one
- * in flight.  Limits (also in the header): the pool does not shrink -- it holds as many ViewBufs as calls were ever
- * enqueued at once, 4 KiB of each memory and one event apiece -- and a call that has to allocate cannot be captured
- * into a graph.
- */
-struct ViewBuf {
-    void *p = nullptr;      /* device */
-    void *host = nullptr;   /* pinned */
-    size_t bytes = 0;
-    hipEvent_t done = nullptr;
-    int device = 0;
-};
-static std::mutex g_view_mutex;
-static std::vector<ViewBuf> g_view_bufs;
-
-static amvpt_status view_buf_take(size_t bytes, ViewBuf &b) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return hip_fail("amvpt_temporal hipGetDevice", (int) e);
-    {
-        std::lock_guard<std::mutex> lock(g_view_mutex);
-        for (size_t i = 0; i < g_view_bufs.size(); ++i) {
-            const ViewBuf &c = g_view_bufs[i];
-            if (c.device != dev || c.bytes < bytes || hipEventQuery(c.done) != hipSuccess) continue;
-            b = c;
-            g_view_bufs.erase(g_view_bufs.begin() + (ptrdiff_t) i);
-            return AMVPT_OK;
-        }
-    }
-    b = ViewBuf{};
-    b.device = dev;
-    b.bytes = (bytes + 4095u) & ~(size_t) 4095u;
-    e = hipMalloc(&b.p, b.bytes);
-    if (e != hipSuccess) { set_error("amvpt_temporal: hipMalloc of the view table failed"); return AMVPT_ERR_OOM; }
-    e = hipHostMalloc(&b.host, b.bytes, hipHostMallocDefault);
-    if (e != hipSuccess) {
-        (void) hipFree(b.p);
-        set_error("amvpt_temporal: hipHostMalloc of the view table's staging block failed");
-        return AMVPT_ERR_OOM;
-    }
-    e = hipEventCreateWithFlags(&b.done, hipEventDisableTiming);
-    if (e != hipSuccess) {
-        (void) hipFree(b.p);
-        (void) hipHostFree(b.host);
-        return hip_fail("amvpt_temporal hipEventCreate", (int) e);
-    }
-    return AMVPT_OK;
-}
-/* behind the launch (or the failed attempt) on `st` */
-static hipError_t view_buf_give(const ViewBuf &b, hipStream_t st) {
-    const hipError_t e = hipEventRecord(b.done, st);
-    std::lock_guard<std::mutex> lock(g_view_mutex);
-    g_view_bufs.push_back(b);
-    return e;
 }
 
 static bool tp_overlap(const void *a, size_t na, const void *b, size_t nb) {
@@ -236,7 +175,7 @@ static amvpt_status temporal_launch(const char *who, void (*k)(Args), Args &A, c
     const uint32_t nv = A.L.multisensor ? A.L.n_views : 1u;
     const size_t vbytes = (size_t) nv * sizeof(amvpt_view_desc);
     ViewBuf vb;
-    if (amvpt_status rc = view_buf_take(vbytes, vb)) return rc;
+    if (amvpt_status rc = view_buf_take("amvpt_temporal", vbytes, vb)) return rc;
     std::memcpy(vb.host, prev_views, vbytes);
     hipError_t e = hipMemcpyAsync(vb.p, vb.host, vbytes, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) {

@@ -3,7 +3,7 @@
 
     python tools/quilt_display.py [scene.xml] [-D key=value ...] [--preset NAME --presets presets.csv]
                                   [--size W H] [--nearest] [--out-dir DIR] [--depth PATH]
-                                  [--denoise [ITER]] [--temporal N [--denoise-variance]]
+                                  [--denoise [ITER]] [--temporal N [--denoise-variance]] [--synth GX GY]
 
 Without arguments: scenes/cbox_grid.xml at a small resolution, the default preset (LKG4x8) with the scene's view
 grid, a 1280 x 720 display, written to out/<scene>_quilt.png and out/<scene>_display.png.  The frame is rendered once;
@@ -13,7 +13,9 @@ frame on the device before both images are made (amvpt.denoise's defaults; ITER 
 renders N frames at the given spp with consecutive seeds through an amvpt.TemporalAccumulator and shows the last one
 (with --denoise, filtered after the accumulation).  --temporal N --denoise-variance filters with the variance-guided
 denoiser of include/amvpt_variance.h instead: the accumulator carries the luminance moments, and the filter is as wide as
-the variance they give (amvpt.VarianceParams' defaults, sigma_plane scaled to the scene).
+the variance they give (amvpt.VarianceParams' defaults, sigma_plane scaled to the scene).  --synth GX GY loads the scene
+a second time with gx=GX gy=GY and shows that denser quilt, synthesized from the rendered one without tracing a path
+(amvpt.ViewSynthesizer, include/amvpt_synth.h; after --denoise where given), and prints how many holes are left.
 """
 import argparse
 import os
@@ -41,9 +43,13 @@ def main():
                     help="accumulate N frames of consecutive seeds (amvpt.TemporalAccumulator) and show the last")
     ap.add_argument("--denoise-variance", action="store_true",
                     help="with --temporal: filter with the variance-guided denoiser (amvpt.VarianceParams' defaults)")
+    ap.add_argument("--synth", type=int, nargs=2, default=None, metavar=("GX", "GY"),
+                    help="show the GX x GY quilt of the same scene, synthesized from the rendered views (amvpt.ViewSynthesizer)")
     a = ap.parse_args()
     if a.denoise_variance and (a.temporal is None or a.denoise is not None):
         ap.error("--denoise-variance needs --temporal and excludes --denoise")
+    if a.synth is not None and a.temporal is not None:
+        ap.error("--synth excludes --temporal")
 
     import amvpt
     import amvpt.display as D
@@ -66,6 +72,8 @@ def main():
     # from the stage run on the frame the render left on the device
     if a.temporal is not None:
         return temporal_frames(a, ap, scene, preset, cnt)
+    if a.synth is not None:
+        return synthesized(a, scene, defines, preset, cnt)
     frame = amvpt.render(scene, seed=a.seed, spp=a.spp, counters=cnt)
     if a.denoise is not None:   # the filtered frame replaces the cached one: the display image below shows it
         q = amvpt.denoise_params_for(scene, iterations=a.denoise)
@@ -105,6 +113,27 @@ def temporal_frames(a, ap, scene, preset, cnt):
         D.write_png(a.depth, D.depth_quilt(scene))
     print("%s: %d frames accumulated (mean history %.2f) -> %s_quilt.png, %s_display.png" % (
         os.path.basename(a.scene), a.temporal, float(acc.count.mean()), stem, stem))
+
+
+def synthesized(a, scene, defines, preset, cnt):
+    """--synth GX GY: one display through a ViewSynthesizer; the quilt is the synthesizer's dense image."""
+    import amvpt
+    import amvpt.display as D
+    dense = amvpt.load_file(a.scene, **dict(defines, gx=a.synth[0], gy=a.synth[1]))
+    vs = amvpt.ViewSynthesizer(dense)
+    denoise = amvpt.denoise_params_for(scene, iterations=a.denoise) if a.denoise is not None else None
+    image = D.display(scene, preset, size=tuple(a.size), nearest=a.nearest, seed=a.seed, spp=a.spp, counters=cnt, denoise=denoise,
+                      synth=vs)
+    os.makedirs(a.out_dir, exist_ok=True)
+    stem = os.path.join(a.out_dir, os.path.splitext(os.path.basename(a.scene))[0])
+    D.write_png(stem + "_quilt.png", D.srgb8(vs.image.cpu().numpy()))
+    D.write_png(stem + "_display.png", image)
+    if a.depth:
+        D.write_png(a.depth, D.depth_quilt(dense))
+    w, h = int(vs.dst_params.film_width), int(vs.dst_params.film_height)
+    print("%s: %d views synthesized from %d rendered ones, quilt %d x %d, %d holes of %d pixels (%d filled) -> %s_quilt.png, "
+          "%s_display.png" % (os.path.basename(a.scene), len(vs.dst_views), scene.describe(0, 0, 0)[2].n_views, w, h, vs.holes,
+                              w * h, int((vs.cover < 0).sum().item()), stem, stem))
 
 
 if __name__ == "__main__":
