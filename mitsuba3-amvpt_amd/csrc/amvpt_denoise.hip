@@ -12,18 +12,16 @@
  */
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <cstdint>
 #include <string>
 
 #include "../../include/amvpt_denoise.h"
 #include "ddenoise.h"
+#include "dtile.h"
 #include "internal.h"
+#include "post_host.h"
 
 namespace amvpt {
-
-static constexpr int kTileW = 32, kTileH = 8;
-static constexpr uint32_t kDenoiseBlock = kTileW * kTileH;
 
 struct DenoiseArgs {
     const float *in, *guides;
@@ -33,127 +31,76 @@ struct DenoiseArgs {
 };
 
 /* the pixel's RGB, and with four channels the alpha of the iteration's input (the image's own, handed down) */
-__device__ __forceinline__ void denoise_store(const DenoiseArgs &A, int x, int y, const float rgb[3]) {
+__host__ __device__ __forceinline__ void denoise_store(const DenoiseArgs &A, int x, int y, const float rgb[3]) {
     const size_t at = ((size_t) y * A.w + (size_t) x) * A.channels;
     A.out[at] = rgb[0], A.out[at + 1] = rgb[1], A.out[at + 2] = rgb[2];
     if (A.channels == 4u) A.out[at + 3] = A.in[at + 3];
 }
 
-__global__ void __launch_bounds__(kDenoiseBlock) k_denoise_direct(DenoiseArgs A) {
-    const int x = (int) (blockIdx.x % A.tiles_x) * kTileW + (int) (threadIdx.x % kTileW);
-    const int y = (int) (blockIdx.x / A.tiles_x) * kTileH + (int) (threadIdx.x / kTileW);
-    if (x >= (int) A.w || y >= (int) A.h) return;
-    const DenoisePlanes P{A.in, A.guides, A.channels, A.w};
+__global__ void __launch_bounds__(kTileBlock) k_denoise_direct(DenoiseArgs A) {
+    const TilePixel t = tile_pixel(A.tiles_x);
+    if (t.x >= (int) A.w || t.y >= (int) A.h) return;
+    const DenoisePlanes P{{A.guides, A.w}, A.in, A.channels};
     float rgb[3];
-    denoise_pixel(P, x, y, (int) A.w, (int) A.h, A.K, rgb);
-    denoise_store(A, x, y, rgb);
+    denoise_pixel(P, t.x, t.y, (int) A.w, (int) A.h, A.K, rgb);
+    denoise_store(A, t.x, t.y, rgb);
 }
 
-/* the staged pixels of one block, plane by plane: consecutive lanes read consecutive 16-byte heads (ds_read_b128)
- * and consecutive dwords of every other plane, so no read conflicts on a bank */
+/* the staged pixels of one block: the guide records and the colour */
 template <int S>
-struct DenoiseTile {
-    static constexpr int kHalo = 2 * S, kW = kTileW + 2 * kHalo, kH = kTileH + 2 * kHalo, kN = kW * kH;
-    float4 head[kN];      /* shape, normal */
-    float view[kN];
-    float pos[3][kN];
-    float rgb[3][kN];
+struct DenoiseTile : GuideTile<2 * S> {
+    float rgb[3][GuideTile<2 * S>::kN];
 };
 
 template <int S>
-struct DenoiseTileSrc {
-    const DenoiseTile<S> &T;
-    int x0, y0;   /* image coordinates of the tile's first staged pixel */
-    __device__ __forceinline__ int at(int x, int y) const { return (y - y0) * DenoiseTile<S>::kW + (x - x0); }
-    __device__ __forceinline__ void head(int x, int y, float g[4]) const {
-        const float4 v = T.head[at(x, y)];
-        g[0] = v.x, g[1] = v.y, g[2] = v.z, g[3] = v.w;
-    }
-    __device__ __forceinline__ float view(int x, int y) const { return T.view[at(x, y)]; }
-    __device__ __forceinline__ void point(int x, int y, float p[3]) const {
-        const int i = at(x, y);
-        p[0] = T.pos[0][i], p[1] = T.pos[1][i], p[2] = T.pos[2][i];
-    }
+struct DenoiseTileSrc : GuideTileSrc<DenoiseTile<S>> {
     __device__ __forceinline__ void color(int x, int y, float c[3]) const {
-        const int i = at(x, y);
-        c[0] = T.rgb[0][i], c[1] = T.rgb[1][i], c[2] = T.rgb[2][i];
+        const int i = this->at(x, y);
+        c[0] = this->T.rgb[0][i], c[1] = this->T.rgb[1][i], c[2] = this->T.rgb[2][i];
     }
 };
 
 template <int S>
-__global__ void __launch_bounds__(kDenoiseBlock) k_denoise_tile(DenoiseArgs A) {
+__global__ void __launch_bounds__(kTileBlock) k_denoise_tile(DenoiseArgs A) {
     using Tile = DenoiseTile<S>;
     __shared__ Tile T;
-    const int bx = (int) (blockIdx.x % A.tiles_x) * kTileW, by = (int) (blockIdx.x / A.tiles_x) * kTileH;
-    const int x0 = bx - Tile::kHalo, y0 = by - Tile::kHalo;
-    /* pixels outside the image stay unstaged: denoise_pixel tests a tap's coordinates before it reads anything */
-    for (int i = (int) threadIdx.x; i < Tile::kN; i += (int) kDenoiseBlock) {
-        const int gx = x0 + i % Tile::kW, gy = y0 + i / Tile::kW;
-        if (gx < 0 || gy < 0 || gx >= (int) A.w || gy >= (int) A.h) continue;
-        const size_t px = (size_t) gy * A.w + (size_t) gx;
+    const TilePixel t = tile_pixel(A.tiles_x);
+    const int x0 = t.bx - Tile::kHalo, y0 = t.by - Tile::kHalo;
+    tile_stage<Tile>(x0, y0, A.w, A.h, [&](int i, size_t px) {
         const float *r = A.guides + 8 * px, *c = A.in + A.channels * px;
-        T.head[i] = make_float4(r[0], r[1], r[2], r[3]);
-        T.pos[0][i] = r[4], T.pos[1][i] = r[5], T.pos[2][i] = r[6];
-        T.view[i] = r[7];
+        T.stage(i, r);
         T.rgb[0][i] = c[0], T.rgb[1][i] = c[1], T.rgb[2][i] = c[2];
-    }
+    });
     __syncthreads();
-    const int x = bx + (int) (threadIdx.x % kTileW), y = by + (int) (threadIdx.x / kTileW);
-    if (x >= (int) A.w || y >= (int) A.h) return;
+    if (t.x >= (int) A.w || t.y >= (int) A.h) return;
     DenoiseStep K = A.K;
     K.step = S;
-    const DenoiseTileSrc<S> src{T, x0, y0};
+    const DenoiseTileSrc<S> src{{T, x0, y0}};
     float rgb[3];
-    denoise_pixel(src, x, y, (int) A.w, (int) A.h, K, rgb);
-    denoise_store(A, x, y, rgb);
-}
-
-/* a visible device is remembered (it does not go away); its absence is asked again on the next call */
-static bool denoise_device_ok() {
-    static std::atomic<bool> seen{false};
-    if (seen.load(std::memory_order_relaxed)) return true;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return false;
-    seen.store(true, std::memory_order_relaxed);
-    return true;
-}
-
-static bool dn_overlap(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t a0 = (uintptr_t) a, b0 = (uintptr_t) b;
-    return a0 < b0 + nb && b0 < a0 + na;
+    denoise_pixel(src, t.x, t.y, (int) A.w, (int) A.h, K, rgb);
+    denoise_store(A, t.x, t.y, rgb);
 }
 
 /* the refusals of both entries */
-static amvpt_status denoise_check(const char *who, const float *image, uint32_t channels, uint32_t w, uint32_t h,
+static amvpt_status denoise_check(const Refusal &R, const float *image, uint32_t channels, uint32_t w, uint32_t h,
                                   const float *guides, const amvpt_denoise_params *p, const float *out, const float *scratch) {
-    const std::string s = std::string(who) + ": ";
-    auto bad = [&](const std::string &what) { set_error(s + what); return AMVPT_ERR_INVALID; };
-    if (!image) return bad("null image");
-    if (!guides) return bad("null guides");
-    if (!p) return bad("null params");
-    if (!out) return bad("null out");
-    if (channels != 3u && channels != 4u) return bad("channels must be 3 or 4, not " + std::to_string(channels));
-    if (w == 0) return bad("width is 0");
-    if (h == 0) return bad("height is 0");
-    if (p->iterations < 1u || p->iterations > 8u) return bad("params: iterations must be 1 .. 8, not " + std::to_string(p->iterations));
-    if (!dn_finite(p->sigma_color) || !(p->sigma_color > 0.f)) return bad("params: sigma_color must be finite and above 0");
-    if (!dn_finite(p->color_floor) || !(p->color_floor > 0.f)) return bad("params: color_floor must be finite and above 0");
-    if (!dn_finite(p->sigma_plane) || !(p->sigma_plane > 0.f)) return bad("params: sigma_plane must be finite and above 0");
-    if (p->normal_squarings > 7u) return bad("params: normal_squarings must be 0 .. 7, not " + std::to_string(p->normal_squarings));
-    if (p->iterations > 1u && !scratch) return bad("null scratch (it may be null only when iterations is 1)");
+    if (!image) return R.bad("null image");
+    if (!guides) return R.bad("null guides");
+    if (!p) return R.bad("null params");
+    if (!out) return R.bad("null out");
+    if (amvpt_status st = check_channels(R, channels)) return st;
+    if (amvpt_status st = check_size(R, w, h)) return st;
+    if (p->iterations < 1u || p->iterations > 8u) return R.bad("params: iterations must be 1 .. 8, not " + std::to_string(p->iterations));
+    if (!pp_finite(p->sigma_color) || !(p->sigma_color > 0.f)) return R.bad("params: sigma_color must be finite and above 0");
+    if (!pp_finite(p->color_floor) || !(p->color_floor > 0.f)) return R.bad("params: color_floor must be finite and above 0");
+    if (!pp_finite(p->sigma_plane) || !(p->sigma_plane > 0.f)) return R.bad("params: sigma_plane must be finite and above 0");
+    if (p->normal_squarings > 7u) return R.bad("params: normal_squarings must be 0 .. 7, not " + std::to_string(p->normal_squarings));
+    if (p->iterations > 1u && !scratch) return R.bad("null scratch (it may be null only when iterations is 1)");
     const size_t npx = (size_t) w * h, nimg = npx * channels * sizeof(float), ngd = npx * 8 * sizeof(float);
-    if (dn_overlap(out, nimg, image, nimg)) return bad("out overlaps the image");
-    if (dn_overlap(out, nimg, guides, ngd)) return bad("out overlaps the guides");
-    if (scratch) {
-        if (dn_overlap(scratch, nimg, image, nimg)) return bad("scratch overlaps the image");
-        if (dn_overlap(scratch, nimg, guides, ngd)) return bad("scratch overlaps the guides");
-        if (dn_overlap(scratch, nimg, out, nimg)) return bad("scratch overlaps out");
-    }
-    return AMVPT_OK;
+    return check_disjoint(R, {{out, nimg, "out"}, {scratch, nimg, "scratch"}}, {{image, nimg, "the image"}, {guides, ngd, "the guides"}});
 }
 
-/* iteration i of n: its constants, and where it reads and writes -- out and scratch take turns so that the last
- * iteration lands in out */
+/* the constants of iteration i */
 static DenoiseStep denoise_step(const amvpt_denoise_params &p, uint32_t i) {
     DenoiseStep K;
     K.inv_s2 = 1.f / (p.sigma_color * p.sigma_color);
@@ -164,7 +111,6 @@ static DenoiseStep denoise_step(const amvpt_denoise_params &p, uint32_t i) {
     K.step = (int32_t) (1u << i);
     return K;
 }
-static float *denoise_dst(uint32_t i, uint32_t n, float *out, float *scratch) { return ((n - 1u - i) & 1u) ? scratch : out; }
 
 } // namespace amvpt
 
@@ -186,19 +132,18 @@ amvpt_denoise_params amvpt_denoise_default_params(void) {
 
 amvpt_status amvpt_denoise_host(const float *image, uint32_t channels, uint32_t width, uint32_t height, const float *guides,
                                 const amvpt_denoise_params *params, float *out, float *scratch) {
-    if (amvpt_status s = denoise_check("amvpt_denoise_host", image, channels, width, height, guides, params, out, scratch)) return s;
+    const Refusal R("amvpt_denoise_host");
+    if (amvpt_status s = denoise_check(R, image, channels, width, height, guides, params, out, scratch)) return s;
     const float *in = image;
     for (uint32_t i = 0; i < params->iterations; ++i) {
-        const DenoiseStep K = denoise_step(*params, i);
-        float *dst = denoise_dst(i, params->iterations, out, scratch);
-        const DenoisePlanes P{in, guides, channels, width};
+        float *dst = pingpong_dst(i, params->iterations, out, scratch);
+        const DenoiseArgs A{in, guides, dst, channels, width, height, 0u, denoise_step(*params, i)};
+        const DenoisePlanes P{{guides, width}, in, channels};
         for (uint32_t y = 0; y < height; ++y)
             for (uint32_t x = 0; x < width; ++x) {
                 float rgb[3];
-                denoise_pixel(P, (int) x, (int) y, (int) width, (int) height, K, rgb);
-                const size_t at = ((size_t) y * width + x) * channels;
-                dst[at] = rgb[0], dst[at + 1] = rgb[1], dst[at + 2] = rgb[2];
-                if (channels == 4u) dst[at + 3] = in[at + 3];
+                denoise_pixel(P, (int) x, (int) y, (int) width, (int) height, A.K, rgb);
+                denoise_store(A, (int) x, (int) y, rgb);
             }
         in = dst;
     }
@@ -208,19 +153,18 @@ amvpt_status amvpt_denoise_host(const float *image, uint32_t channels, uint32_t 
 amvpt_status amvpt_denoise(const float *image_device, uint32_t channels, uint32_t width, uint32_t height,
                            const float *guides_device, const amvpt_denoise_params *params, float *out_device,
                            float *scratch_device, void *stream) {
-    if (amvpt_status s = denoise_check("amvpt_denoise", image_device, channels, width, height, guides_device, params, out_device,
-                                       scratch_device))
+    const Refusal R("amvpt_denoise");
+    if (amvpt_status s = denoise_check(R, image_device, channels, width, height, guides_device, params, out_device, scratch_device))
         return s;
-    /* pixel coordinates are ints, and one launch of 32 x 8 tiles covers the image */
-    if (width > 0x7fffff00u || height > 0x7fffff00u) { set_error("amvpt_denoise: width or height above 2^31 - 256"); return AMVPT_ERR_INVALID; }
-    const uint64_t tx = (width + (uint32_t) kTileW - 1u) / (uint32_t) kTileW, ty = (height + (uint32_t) kTileH - 1u) / (uint32_t) kTileH;
-    if (tx * ty >= (1ull << 31)) { set_error("amvpt_denoise: width x height above 2^31 tiles of 32 x 8 pixels"); return AMVPT_ERR_INVALID; }
-    if (!denoise_device_ok()) { set_error("amvpt_denoise: no HIP device visible"); return AMVPT_ERR_NO_DEVICE; }
-    const dim3 grid((uint32_t) (tx * ty)), block(kDenoiseBlock);
+    if (amvpt_status s = check_size_tiles(R, width, height)) return s;
+    if (amvpt_status s = R.need_device()) return s;
+    uint64_t tx, ty;
+    tile_grid(width, height, tx, ty);
+    const dim3 grid((uint32_t) (tx * ty)), block(kTileBlock);
     hipStream_t st = (hipStream_t) stream;
     const float *in = image_device;
     for (uint32_t i = 0; i < params->iterations; ++i) {
-        float *dst = denoise_dst(i, params->iterations, out_device, scratch_device);
+        float *dst = pingpong_dst(i, params->iterations, out_device, scratch_device);
         const DenoiseArgs A{in, guides_device, dst, channels, width, height, (uint32_t) tx, denoise_step(*params, i)};
         if (i == 0) hipLaunchKernelGGL(k_denoise_tile<1>, grid, block, 0, st, A);
         else if (i == 1) hipLaunchKernelGGL(k_denoise_tile<2>, grid, block, 0, st, A);

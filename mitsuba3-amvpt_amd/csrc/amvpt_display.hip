@@ -10,7 +10,6 @@
  */
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <cmath>
 #include <cstdint>
 #include <string>
@@ -18,6 +17,7 @@
 #include "../../include/amvpt_display.h"
 #include "ddisplay.h"
 #include "internal.h"
+#include "post_host.h"
 
 namespace amvpt {
 
@@ -154,16 +154,6 @@ static amvpt_status srgb8_check(const char *who, const void *in, uint32_t ch, ui
     return AMVPT_OK;
 }
 
-/* a visible device is remembered (it does not go away); its absence is asked again on the next call */
-static bool display_device_ok() {
-    static std::atomic<bool> seen{false};
-    if (seen.load(std::memory_order_relaxed)) return true;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return false;
-    seen.store(true, std::memory_order_relaxed);
-    return true;
-}
-
 /* one launch covers the image: HIP refuses a grid of 2^32 threads or more, so an image is held to 2^33 pixels
  * (2^23 blocks of 256 threads, four pixels each) and a larger one is refused by name before the launch */
 static constexpr uint64_t kMaxDisplayPixels = 1ull << 33;
@@ -202,7 +192,7 @@ amvpt_status amvpt_srgb8(const float *image, uint32_t channels, uint32_t width, 
     if (amvpt_status s = srgb8_check("amvpt_srgb8", image, channels, width, height, out)) return s;
     const uint64_t npx = (uint64_t) width * height;
     if (npx > kMaxDisplayPixels) { set_error("amvpt_srgb8: width * height above 2^33 pixels"); return AMVPT_ERR_INVALID; }
-    if (!display_device_ok()) { set_error("amvpt_srgb8: no HIP device visible"); return AMVPT_ERR_NO_DEVICE; }
+    if (!device_ok()) { set_error("amvpt_srgb8: no HIP device visible"); return AMVPT_ERR_NO_DEVICE; }
     const bool vec = ((uintptr_t) image & 15u) == 0 && ((uintptr_t) out & 3u) == 0;
     const dim3 grid(display_blocks(npx)), block(kDisplayBlock);
     hipStream_t st = (hipStream_t) stream;
@@ -260,7 +250,7 @@ amvpt_status amvpt_interlace(const uint8_t *src, uint32_t src_w, uint32_t src_h,
         return s;
     const uint64_t npx = (uint64_t) dst_w * dst_h;
     if (npx > kMaxDisplayPixels) { set_error("amvpt_interlace: dst_w * dst_h above 2^33 pixels"); return AMVPT_ERR_INVALID; }
-    if (!display_device_ok()) { set_error("amvpt_interlace: no HIP device visible"); return AMVPT_ERR_NO_DEVICE; }
+    if (!device_ok()) { set_error("amvpt_interlace: no HIP device visible"); return AMVPT_ERR_NO_DEVICE; }
     const dim3 grid(display_blocks(npx)), block(kDisplayBlock);
     hipStream_t st = (hipStream_t) stream;
     if (((uintptr_t) dst & 3u) == 0) hipLaunchKernelGGL((k_interlace<true>), grid, block, 0, st, src, dst, P);

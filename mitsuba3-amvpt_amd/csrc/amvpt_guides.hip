@@ -8,7 +8,6 @@
  */
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <cmath>
 #include <cstdint>
 #include <string>
@@ -16,6 +15,7 @@
 #include "../../include/amvpt_guides.h"
 #include "dguides.h"
 #include "internal.h"
+#include "post_host.h"
 
 namespace amvpt {
 
@@ -92,16 +92,6 @@ __global__ void __launch_bounds__(kGuideBlock) k_depth8(const float *__restrict_
     for (uint64_t p = p0; p < npx; ++p, dst += 3) dst[0] = dst[1] = dst[2] = depth8_value(depth[p], P);
 }
 
-/* a visible device is remembered (it does not go away); its absence is asked again on the next call */
-static bool guides_device_ok() {
-    static std::atomic<bool> seen{false};
-    if (seen.load(std::memory_order_relaxed)) return true;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return false;
-    seen.store(true, std::memory_order_relaxed);
-    return true;
-}
-
 /* one launch covers the plane: HIP refuses a grid of 2^32 threads or more */
 static constexpr uint64_t kMaxGuidePixels = 1ull << 31;
 
@@ -140,7 +130,7 @@ uint32_t amvpt_guides_version(void) { return AMVPT_GUIDES_VERSION; }
 
 amvpt_status amvpt_guides(amvpt_scene *scene, const amvpt_view_desc *views, const amvpt_params *params,
                           const uint32_t rect[4], float *out_device, void *stream) {
-    if (!guides_device_ok()) { set_error("amvpt_guides: no HIP device visible"); return AMVPT_ERR_NO_DEVICE; }
+    if (!device_ok()) { set_error("amvpt_guides: no HIP device visible"); return AMVPT_ERR_NO_DEVICE; }
     return guides_impl(scene, views, params, rect, out_device, stream);
 }
 
@@ -164,7 +154,7 @@ amvpt_status amvpt_guide_depth(const float *guides_device, const amvpt_view_desc
                                uint64_t n_pixels, float *depth_device, void *stream) {
     if (amvpt_status s = depth_check("amvpt_guide_depth", guides_device, views, n_views, depth_device)) return s;
     if (n_pixels > kMaxGuidePixels) { set_error("amvpt_guide_depth: n_pixels above 2^31"); return AMVPT_ERR_INVALID; }
-    if (!guides_device_ok()) { set_error("amvpt_guide_depth: no HIP device visible"); return AMVPT_ERR_NO_DEVICE; }
+    if (!device_ok()) { set_error("amvpt_guide_depth: no HIP device visible"); return AMVPT_ERR_NO_DEVICE; }
     if (n_pixels == 0) return AMVPT_OK;
     const dim3 grid((uint32_t) ((n_pixels + kGuideBlock - 1) / kGuideBlock)), block(kGuideBlock);
     hipStream_t st = (hipStream_t) stream;
@@ -197,7 +187,7 @@ amvpt_status amvpt_guide_depth_range_host(const float *depth, uint64_t n, float 
 amvpt_status amvpt_guide_depth_range(const float *depth_device, uint64_t n, float near_far_host[2], void *stream) {
     if (n && !depth_device) { set_error("amvpt_guide_depth_range: null depth"); return AMVPT_ERR_INVALID; }
     if (!near_far_host) { set_error("amvpt_guide_depth_range: null near_far_host"); return AMVPT_ERR_INVALID; }
-    if (!guides_device_ok()) { set_error("amvpt_guide_depth_range: no HIP device visible"); return AMVPT_ERR_NO_DEVICE; }
+    if (!device_ok()) { set_error("amvpt_guide_depth_range: no HIP device visible"); return AMVPT_ERR_NO_DEVICE; }
     hipStream_t st = (hipStream_t) stream;
     uint32_t mm[2] = {kDepthKeyMin0, kDepthKeyMax0};
     if (n) {
@@ -241,7 +231,7 @@ amvpt_status amvpt_depth8(const float *depth_device, uint32_t w, uint32_t h, flo
     if (amvpt_status s = depth8_check("amvpt_depth8", depth_device, w, h, near, far, out_device, P)) return s;
     const uint64_t npx = (uint64_t) w * h;
     if (npx > 4 * kMaxGuidePixels) { set_error("amvpt_depth8: w * h above 2^33 pixels"); return AMVPT_ERR_INVALID; }
-    if (!guides_device_ok()) { set_error("amvpt_depth8: no HIP device visible"); return AMVPT_ERR_NO_DEVICE; }
+    if (!device_ok()) { set_error("amvpt_depth8: no HIP device visible"); return AMVPT_ERR_NO_DEVICE; }
     const uint64_t per = (uint64_t) kGuideBlock * kPxPerThread;
     const dim3 grid((uint32_t) ((npx + per - 1) / per)), block(kGuideBlock);
     hipStream_t st = (hipStream_t) stream;

@@ -13,14 +13,9 @@
  * and a tap asks for them in this order, so that a tap stopped by its shape or view fetches no colour and no point.
  */
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include <cstddef>
-#include <cstdint>
+#include "dpost.h"
 
 namespace amvpt {
-
-#define DHD __host__ __device__ __forceinline__
 
 /* what one iteration needs beyond its planes; the floats are computed once on the host (amvpt_denoise.hip) */
 struct DenoiseStep {
@@ -31,30 +26,11 @@ struct DenoiseStep {
     int32_t step;        /* 2^i */
 };
 
-DHD bool dn_finite(float f) {
-    uint32_t u;
-    __builtin_memcpy(&u, &f, 4);
-    return (u & 0x7f800000u) != 0x7f800000u;
-}
-DHD float dn_dot(const float *a, const float *b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-/* hk = {1/16, 1/4, 3/8, 1/4, 1/16} at i = -2 .. 2, as selects: no indexed table in registers */
-DHD float dn_hk(int i) { return i == 0 ? 0.375f : ((i == 1 || i == -1) ? 0.25f : 0.0625f); }
-
 /* planes in memory, row-major: image h x w x channels, guides h x w x 8 */
-struct DenoisePlanes {
-    const float *image, *guides;
-    uint32_t channels, w;
-    DHD size_t at(int x, int y) const { return (size_t) y * w + (size_t) x; }
-    DHD void head(int x, int y, float g[4]) const {
-        const float *r = guides + 8 * at(x, y);
-        g[0] = r[0], g[1] = r[1], g[2] = r[2], g[3] = r[3];
-    }
-    DHD float view(int x, int y) const { return guides[8 * at(x, y) + 7]; }
-    DHD void point(int x, int y, float p[3]) const {
-        const float *r = guides + 8 * at(x, y) + 4;
-        p[0] = r[0], p[1] = r[1], p[2] = r[2];
-    }
-    DHD void color(int x, int y, float c[3]) const {
+struct DenoisePlanes : GuidePlanes {
+    const float *image;
+    uint32_t channels;
+    PP_HD void color(int x, int y, float c[3]) const {
         const float *r = image + channels * at(x, y);
         c[0] = r[0], c[1] = r[1], c[2] = r[2];
     }
@@ -62,14 +38,14 @@ struct DenoisePlanes {
 
 /* out = the filtered RGB of pixel (x, y) of a w x h image: one iteration of the definition */
 template <class Src>
-DHD void denoise_pixel(const Src &S, int x, int y, int w, int h, const DenoiseStep &K, float out[3]) {
+PP_HD void denoise_pixel(const Src &S, int x, int y, int w, int h, const DenoiseStep &K, float out[3]) {
     float g0[4], c[3], p0[3] = {0.f, 0.f, 0.f};
     S.head(x, y, g0);
     const float v0 = S.view(x, y);
     S.color(x, y, c);
     const bool hit = g0[0] >= 0.f;
     if (hit) S.point(x, y, p0);
-    const float m = dn_dot(c, c) + K.floor2;
+    const float m = pp_dot(c, c) + K.floor2;
     const float k = K.inv_s2 / m;
     float sum[3] = {0.f, 0.f, 0.f}, sum_w = 0.f;
     for (int dy = -2; dy <= 2; ++dy) {
@@ -84,22 +60,11 @@ DHD void denoise_pixel(const Src &S, int x, int y, int w, int h, const DenoiseSt
             if (g[0] != g0[0] || S.view(qx, qy) != v0) continue;   /* another shape (or hit against miss), another view */
             float cq[3];
             S.color(qx, qy, cq);
-            if (!dn_finite(cq[0]) || !dn_finite(cq[1]) || !dn_finite(cq[2])) continue;
+            if (!pp_finite3(cq)) continue;
             const float d[3] = {cq[0] - c[0], cq[1] - c[1], cq[2] - c[2]};
-            const float wc = 1.f / (1.f + dn_dot(d, d) * k);
-            float wgt = (dn_hk(dy) * dn_hk(dx)) * wc;
-            if (hit) {
-                float wn = dn_dot(g0 + 1, g + 1);
-                wn = wn > 0.f ? wn : 0.f;
-                for (uint32_t i = 0; i < K.squarings; ++i) wn = wn * wn;
-                float pq[3];
-                S.point(qx, qy, pq);
-                const float e[3] = {pq[0] - p0[0], pq[1] - p0[1], pq[2] - p0[2]};
-                float t = dn_dot(g0 + 1, e);
-                t = (t < 0.f ? -t : t) * K.inv_sp;
-                const float wp = 1.f / (1.f + t * t);
-                wgt = wgt * (wn * wp);
-            }
+            const float wc = 1.f / (1.f + pp_dot(d, d) * k);
+            float wgt = (pp_hk(dy) * pp_hk(dx)) * wc;
+            if (hit) wgt = wgt * pp_guide_weight<false>(S, qx, qy, g0, p0, g, K.inv_sp, K.squarings);
             sum[0] = sum[0] + wgt * cq[0];
             sum[1] = sum[1] + wgt * cq[1];
             sum[2] = sum[2] + wgt * cq[2];
@@ -111,7 +76,5 @@ DHD void denoise_pixel(const Src &S, int x, int y, int w, int h, const DenoiseSt
     out[1] = ok ? sum[1] / sum_w : c[1];
     out[2] = ok ? sum[2] / sum_w : c[2];
 }
-
-#undef DHD
 
 } // namespace amvpt

@@ -2,8 +2,8 @@
  * dsynth.h -- the per-pixel functions of the view synthesis (include/amvpt_synth.h, which holds the normative
  * definition): synth_pixel is stage 1, the cross-view gather, and synth_fill_pixel one iteration of stage 2, the hole
  * fill.  The kernels of amvpt_synth.hip and its host-only entries call these same functions.  Weights, sums and stops
- * are unfused float32 (-ffp-contract=off, correctly rounded division and square root); the projection, the tile layout
- * and the helpers are dtemporal.h's, unchanged.  Host and device agree bit for bit.
+ * are unfused float32 (-ffp-contract=off, correctly rounded division and square root); the projection and the tile layout
+ * are dtemporal.h's, the hard stops and the bilinear footprint dpost.h's.  Host and device agree bit for bit.
  *
  * A tap fetches its fields in the order of the stops: the guide record (two 16-byte halves), then the colour -- a tap
  * stopped by its view or shape fetches no colour.  The loop over the source views is uniform across a wave, and the
@@ -13,8 +13,6 @@
 #include "dtemporal.h"
 
 namespace amvpt {
-
-#define SHD __host__ __device__ __forceinline__
 
 struct SynthArgs {
     const float *src_image, *src_guides, *dst_guides;
@@ -36,7 +34,7 @@ struct SynthFillArgs {
 };
 
 /* source view s, the same for every lane of the wave: what the projection reads and the camera's origin */
-SHD TemporalView sy_fetch_view(const amvpt_view_desc *views, uint32_t s, float O[3]) {
+PP_HD TemporalView sy_fetch_view(const amvpt_view_desc *views, uint32_t s, float O[3]) {
 #if defined(__HIP_DEVICE_COMPILE__)
     typedef __attribute__((address_space(4))) const amvpt_view_desc uniform_view;
     const uint32_t s0 = (uint32_t) __builtin_amdgcn_readfirstlane((int) s);
@@ -48,20 +46,12 @@ SHD TemporalView sy_fetch_view(const amvpt_view_desc *views, uint32_t s, float O
     return tp_view(U);
 }
 
-SHD bool sy_finite(const float *c, uint32_t channels) {
-    return tp_finite(c[0]) && tp_finite(c[1]) && tp_finite(c[2]) && (channels != 4u || tp_finite(c[3]));
-}
-
-/* the normal and plane stops of a tap with the record q against the pixel's record g */
-SHD bool sy_same_surface(const float *g, const float *q, float normal_cos, float plane_tol) {
-    if (tp_dot(g + 1, q + 1) < normal_cos) return false;
-    const float e[3] = {q[4] - g[4], q[5] - g[5], q[6] - g[6]};
-    const float t = tp_dot(g + 1, e);
-    return !((t < 0.f ? -t : t) > plane_tol);
+PP_HD bool sy_finite(const float *c, uint32_t channels) {
+    return pp_finite(c[0]) && pp_finite(c[1]) && pp_finite(c[2]) && (channels != 4u || pp_finite(c[3]));
 }
 
 /* stage 1, pixel (lx, ly) of the target rectangle: colour and cover */
-SHD void synth_pixel(const SynthArgs &A, int32_t lx, int32_t ly) {
+PP_HD void synth_pixel(const SynthArgs &A, int32_t lx, int32_t ly) {
     const TemporalLayout &S = A.S, &D = A.D;
     const uint32_t C = A.channels;
     const size_t at = (size_t) ly * (size_t) D.rw + (size_t) lx;
@@ -83,37 +73,33 @@ SHD void synth_pixel(const SynthArgs &A, int32_t lx, int32_t ly) {
     if (ok && g[0] >= 0.f) {
         const float *Ot = A.dst_origins + 3 * (size_t) t;
         const float dt[3] = {Ot[0] - g[4], Ot[1] - g[5], Ot[2] - g[6]};
-        const float lt = __builtin_sqrtf(tp_dot(dt, dt));
+        const float lt = __builtin_sqrtf(pp_dot(dt, dt));
         for (uint32_t s = 0; s < ns; ++s) {
             float Os[3], uvx, uvy;
             const TemporalView V = sy_fetch_view(A.src_views, s, Os);
             if (!tp_project(V, g + 4, uvx, uvy)) continue;
             const float ds[3] = {Os[0] - g[4], Os[1] - g[5], Os[2] - g[6]};
-            const float ls = __builtin_sqrtf(tp_dot(ds, ds));
+            const float ls = __builtin_sqrtf(pp_dot(ds, ds));
             const float d = lt * ls;
             float wv = 1.f;
             if (d > 0.f) {
-                const float c = tp_dot(dt, ds) / d;
+                const float c = pp_dot(dt, ds) / d;
                 float a = 1.f - c;
                 a = a > 0.f ? a : 0.f;
                 wv = 1.f / (1.f + a * A.view_falloff);
             }
             int32_t tx0, ty0;
             tp_tile(S, s, tx0, ty0);
-            const float ftx = (float) tx0, fty = (float) ty0;
-            const float fx = ftx + uvx, fy = fty + uvy;
-            const float sx = fx - .5f, sy = fy - .5f;
-            if (!(sx >= ftx - 1.f && sx < ftx + (float) S.tw && sy >= fty - 1.f && sy < fty + (float) S.th)) continue;
-            const int32_t x0 = tp_floor(sx), y0 = tp_floor(sy);
-            const float ax = sx - (float) x0, ay = sy - (float) y0;
+            Footprint F;
+            if (!pp_footprint(tx0, ty0, S.tw, S.th, uvx, uvy, F)) continue;
             const float fs = (float) s;
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                const int32_t qy = y0 + j;
+                const int32_t qy = F.y0 + j;
                 if (qy < ty0 || qy >= ty0 + S.th) continue;
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
-                    const int32_t qx = x0 + i;
+                    const int32_t qx = F.x0 + i;
                     if (qx < tx0 || qx >= tx0 + S.tw) continue;
                     const size_t qa = (size_t) qy * (size_t) S.rw + (size_t) qx;
                     const float *rq = A.src_guides + 8 * qa;
@@ -122,8 +108,8 @@ SHD void synth_pixel(const SynthArgs &A, int32_t lx, int32_t ly) {
                     const float *cq = A.src_image + C * qa;
                     const float col[4] = {cq[0], cq[1], cq[2], C == 4u ? cq[3] : 0.f};
                     if (!sy_finite(col, C)) continue;
-                    if (!sy_same_surface(g, q, A.normal_cos, A.plane_tol)) continue;
-                    const float w = ((i ? ax : 1.f - ax) * (j ? ay : 1.f - ay)) * wv;
+                    if (!pp_same_surface(g, q, A.normal_cos, A.plane_tol)) continue;
+                    const float w = F.weight(i, j) * wv;
                     sw = sw + w;
                     sc[0] = sc[0] + w * col[0];
                     sc[1] = sc[1] + w * col[1];
@@ -162,11 +148,8 @@ SHD void synth_pixel(const SynthArgs &A, int32_t lx, int32_t ly) {
     }
 }
 
-/* hk = {1/16, 1/4, 3/8, 1/4, 1/16} at i = -2 .. 2, as selects: no indexed table in registers */
-SHD float sy_hk(int i) { return i == 0 ? 0.375f : ((i == 1 || i == -1) ? 0.25f : 0.0625f); }
-
 /* stage 2, one iteration at pixel (x, y) */
-SHD void synth_fill_pixel(const SynthFillArgs &A, int32_t x, int32_t y) {
+PP_HD void synth_fill_pixel(const SynthFillArgs &A, int32_t x, int32_t y) {
     const uint32_t C = A.channels;
     const size_t at = (size_t) y * (size_t) A.w + (size_t) x;
     float *o = A.out + C * at;
@@ -198,9 +181,9 @@ SHD void synth_fill_pixel(const SynthFillArgs &A, int32_t x, int32_t y) {
             if (!sy_finite(col, C)) continue;
             if (hit) {
                 const float q[8] = {q0, rq[1], rq[2], rq[3], rq[4], rq[5], rq[6], q7};
-                if (!sy_same_surface(g, q, A.normal_cos, A.plane_tol)) continue;
+                if (!pp_same_surface(g, q, A.normal_cos, A.plane_tol)) continue;
             }
-            const float w = sy_hk(dy) * sy_hk(dx);
+            const float w = pp_hk(dy) * pp_hk(dx);
             sw = sw + w;
             sc[0] = sc[0] + w * col[0];
             sc[1] = sc[1] + w * col[1];
@@ -218,7 +201,5 @@ SHD void synth_fill_pixel(const SynthFillArgs &A, int32_t x, int32_t y) {
         A.cover_out[at] = 0.f;
     }
 }
-
-#undef SHD
 
 } // namespace amvpt

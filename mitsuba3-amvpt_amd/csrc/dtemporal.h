@@ -15,16 +15,10 @@
  * moments add sits behind `if constexpr`, so the first instance compiles to what it was without them.
  */
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include <cstddef>
-#include <cstdint>
-
 #include "../../include/amvpt.h"
+#include "dpost.h"
 
 namespace amvpt {
-
-#define THD __host__ __device__ __forceinline__
 
 /* the quilt's tiles (amvpt_temporal.h "Layout") and the rectangle the planes hold */
 struct TemporalLayout {
@@ -51,22 +45,10 @@ struct TemporalMomentsArgs : TemporalArgs {
 template <class Args> struct tp_moments { static constexpr bool value = false; };
 template <> struct tp_moments<TemporalMomentsArgs> { static constexpr bool value = true; };
 
-THD bool tp_finite(float f) {
-    uint32_t u;
-    __builtin_memcpy(&u, &f, 4);
-    return (u & 0x7f800000u) != 0x7f800000u;
-}
-THD bool tp_finite3(const float *c) { return tp_finite(c[0]) && tp_finite(c[1]) && tp_finite(c[2]); }
-THD float tp_dot(const float *a, const float *b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-THD float tp_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+PP_HD float tp_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 /* row r of a Transform4f applied to the point q: the terms of xf_point / xf_point_affine */
-THD float tp_row(const float *m, int r, const float *q) {
+PP_HD float tp_row(const float *m, int r, const float *q) {
     return tp_fma(m[4 * r + 2], q[2], tp_fma(m[4 * r + 1], q[1], tp_fma(m[4 * r], q[0], m[4 * r + 3])));
-}
-/* floor of a float in [-1, 2^24) by truncation and a correction */
-THD int32_t tp_floor(float s) {
-    const int32_t i = (int32_t) s;
-    return (float) i > s ? i - 1 : i;
 }
 
 /* the fields of a view the projection reads */
@@ -75,7 +57,7 @@ struct TemporalView {
     float near_clip, far_clip, resolution[2], pp_offset[2], aperture_radius, focus_distance;
     uint32_t type;
 };
-template <class VT> THD TemporalView tp_view(const VT &V) {
+template <class VT> PP_HD TemporalView tp_view(const VT &V) {
     TemporalView T;
     for (int i = 0; i < 12; ++i) T.to_world_inv[i] = V.to_world_inv[i];
     for (int i = 0; i < 16; ++i) T.camera_to_sample[i] = V.camera_to_sample[i];
@@ -88,7 +70,7 @@ template <class VT> THD TemporalView tp_view(const VT &V) {
 }
 
 /* camera_uv(V, P, .5, .5): false when the camera-space z is outside the clip range or not above 0 */
-THD bool tp_project(const TemporalView &V, const float *P, float &uvx, float &uvy) {
+PP_HD bool tp_project(const TemporalView &V, const float *P, float &uvx, float &uvy) {
     const float ref[3] = {tp_row(V.to_world_inv, 0, P), tp_row(V.to_world_inv, 1, P), tp_row(V.to_world_inv, 2, P)};
     if (!(ref[2] >= V.near_clip && ref[2] <= V.far_clip && ref[2] > 0.f)) return false;
     const float *s = V.camera_to_sample;
@@ -114,7 +96,7 @@ THD bool tp_project(const TemporalView &V, const float *P, float &uvx, float &uv
 
 /* view v of the table.  On the device a wave whose lanes all ask for one view (a wave is two rows of 32 pixels: every
  * wave of a quilt whose tile width is a multiple of 32) fetches it once with scalar loads instead of once per lane */
-THD TemporalView tp_fetch_view(const amvpt_view_desc *views, uint32_t v) {
+PP_HD TemporalView tp_fetch_view(const amvpt_view_desc *views, uint32_t v) {
 #if defined(__HIP_DEVICE_COMPILE__)
     const uint32_t v0 = (uint32_t) __builtin_amdgcn_readfirstlane((int) v);
     if (__ballot(v != v0) == 0ull) {
@@ -126,7 +108,7 @@ THD TemporalView tp_fetch_view(const amvpt_view_desc *views, uint32_t v) {
 }
 
 /* the first pixel of view v's tile, in quilt pixels */
-THD void tp_tile(const TemporalLayout &L, uint32_t v, int32_t &tx0, int32_t &ty0) {
+PP_HD void tp_tile(const TemporalLayout &L, uint32_t v, int32_t &tx0, int32_t &ty0) {
     uint32_t col = 0, row = 0;
     if (L.multisensor) {
         if (L.batch) col = L.rev_x ? L.n_views - 1u - v : v;
@@ -141,7 +123,7 @@ THD void tp_tile(const TemporalLayout &L, uint32_t v, int32_t &tx0, int32_t &ty0
 
 /* the history of a hit pixel: the four taps around its reprojection; n_prev = 0 when nothing is accepted.  hm: the
  * history of the moments (the moments instance alone) */
-template <class Args> THD float tp_gather(const Args &A, const float *g, float h[3], float hm[2]) {
+template <class Args> PP_HD float tp_gather(const Args &A, const float *g, float h[3], float hm[2]) {
     constexpr bool kMoments = tp_moments<Args>::value;
     const TemporalLayout &L = A.L;
     const uint32_t nv = L.multisensor ? L.n_views : 1u;
@@ -152,22 +134,18 @@ template <class Args> THD float tp_gather(const Args &A, const float *g, float h
     if (!tp_project(V, g + 4, uvx, uvy)) return 0.f;
     int32_t tx0, ty0;
     tp_tile(L, v, tx0, ty0);
-    const float ftx = (float) tx0, fty = (float) ty0;
-    const float fx = ftx + uvx, fy = fty + uvy;
-    const float sx = fx - .5f, sy = fy - .5f;
-    if (!(sx >= ftx - 1.f && sx < ftx + (float) L.tw && sy >= fty - 1.f && sy < fty + (float) L.th)) return 0.f;
-    const int32_t x0 = tp_floor(sx), y0 = tp_floor(sy);
-    const float ax = sx - (float) x0, ay = sy - (float) y0;
+    Footprint F;
+    if (!pp_footprint(tx0, ty0, L.tw, L.th, uvx, uvy, F)) return 0.f;
     float sw = 0.f, sn = 0.f, sc[3] = {0.f, 0.f, 0.f};
     float n_lo = __builtin_huge_valf(), n_hi = 0.f;   /* the range of the accepted counts */
     float sm[2] = {0.f, 0.f};
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-        const int32_t qy = y0 + j;
+        const int32_t qy = F.y0 + j;
         if (qy < ty0 || qy >= ty0 + L.th || qy < L.ry0 || qy >= L.ry0 + L.rh) continue;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            const int32_t qx = x0 + i;
+            const int32_t qx = F.x0 + i;
             if (qx < tx0 || qx >= tx0 + L.tw || qx < L.rx0 || qx >= L.rx0 + L.rw) continue;
             const size_t at = (size_t) (qy - L.ry0) * (size_t) L.rw + (size_t) (qx - L.rx0);
             const float *r = A.hist_guides + 8 * at;
@@ -177,12 +155,9 @@ template <class Args> THD float tp_gather(const Args &A, const float *g, float h
             if (!(cnt >= 1.f)) continue;
             const float *hc = A.hist_image + A.channels * at;
             const float col[3] = {hc[0], hc[1], hc[2]};
-            if (!tp_finite3(col)) continue;
-            if (tp_dot(g + 1, q + 1) < A.normal_cos) continue;
-            const float e[3] = {q[4] - g[4], q[5] - g[5], q[6] - g[6]};
-            const float t = tp_dot(g + 1, e);
-            if ((t < 0.f ? -t : t) > A.plane_tol) continue;
-            const float w = (i ? ax : 1.f - ax) * (j ? ay : 1.f - ay);
+            if (!pp_finite3(col)) continue;
+            if (!pp_same_surface(g, q, A.normal_cos, A.plane_tol)) continue;
+            const float w = F.weight(i, j);
             sw = sw + w;
             sc[0] = sc[0] + w * col[0];
             sc[1] = sc[1] + w * col[1];
@@ -206,14 +181,14 @@ template <class Args> THD float tp_gather(const Args &A, const float *g, float h
 }
 
 /* pixel (lx, ly) of the rectangle: both outputs, and with the moments instance the third */
-template <class Args> THD void temporal_pixel(const Args &A, int32_t lx, int32_t ly) {
+template <class Args> PP_HD void temporal_pixel(const Args &A, int32_t lx, int32_t ly) {
     constexpr bool kMoments = tp_moments<Args>::value;
     const size_t at = (size_t) ly * (size_t) A.L.rw + (size_t) lx;
     const float *cp = A.image + A.channels * at;
     const float c[3] = {cp[0], cp[1], cp[2]};
     float *o = A.out_image + A.channels * at;
     if (A.channels == 4u) o[3] = cp[3];
-    if (!tp_finite3(c)) {
+    if (!pp_finite3(c)) {
         o[0] = c[0], o[1] = c[1], o[2] = c[2];
         A.out_count[at] = 0.f;
         if constexpr (kMoments) A.out_moments[2 * at] = 0.f, A.out_moments[2 * at + 1] = 0.f;
@@ -221,7 +196,7 @@ template <class Args> THD void temporal_pixel(const Args &A, int32_t lx, int32_t
     }
     float m[2] = {0.f, 0.f}, hm[2] = {0.f, 0.f};
     if constexpr (kMoments) {
-        const float l = (0.2126f * c[0] + 0.7152f * c[1]) + 0.0722f * c[2];
+        const float l = pp_lum(c);
         m[0] = l, m[1] = l * l;
     }
     const float *r = A.guides + 8 * at;
@@ -234,7 +209,7 @@ template <class Args> THD void temporal_pixel(const Args &A, int32_t lx, int32_t
             if (cnt >= 1.f) {
                 const float *hc = A.hist_image + A.channels * at;
                 const float col[3] = {hc[0], hc[1], hc[2]};
-                if (tp_finite3(col)) {
+                if (pp_finite3(col)) {
                     h[0] = col[0], h[1] = col[1], h[2] = col[2], n_prev = cnt;
                     if constexpr (kMoments) hm[0] = A.hist_moments[2 * at], hm[1] = A.hist_moments[2 * at + 1];
                 }
@@ -261,7 +236,5 @@ template <class Args> THD void temporal_pixel(const Args &A, int32_t lx, int32_t
         if constexpr (kMoments) A.out_moments[2 * at] = m[0], A.out_moments[2 * at + 1] = m[1];
     }
 }
-
-#undef THD
 
 } // namespace amvpt

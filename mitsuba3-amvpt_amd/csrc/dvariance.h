@@ -20,31 +20,11 @@
  * so that the kernel whose taps go to memory can still keep the prefilter's nine in LDS.
  */
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include <cstddef>
-#include <cstdint>
-
-#include "ddenoise.h"
+#include "dpost.h"
 
 namespace amvpt {
 
-#define VHD __host__ __device__ __forceinline__
-
-VHD float vr_lum(const float *c) { return (0.2126f * c[0] + 0.7152f * c[1]) + 0.0722f * c[2]; }
-VHD float vr_max0(float x) { return x > 0.f ? x : 0.f; }
-
-/* wn*wp of amvpt_denoise between a centre (normal n0 = g0 + 1, hit point p0) and a tap (g, pq) */
-VHD float vr_guide_weight(const float *g0, const float *p0, const float *g, const float *pq, float inv_sp, uint32_t squarings) {
-    float wn = dn_dot(g0 + 1, g + 1);
-    wn = wn > 0.f ? wn : 0.f;
-    for (uint32_t i = 0; i < squarings; ++i) wn = wn * wn;
-    const float e[3] = {pq[0] - p0[0], pq[1] - p0[1], pq[2] - p0[2]};
-    float t = dn_dot(g0 + 1, e);
-    t = (t < 0.f ? -t : t) * inv_sp;
-    const float wp = 1.f / (1.f + t * t);
-    return wn * wp;
-}
+PP_HD float vr_max0(float x) { return x > 0.f ? x : 0.f; }
 
 /* ---- stage 2 ------------------------------------------------------------------------------------------------------ */
 
@@ -59,40 +39,29 @@ struct VarianceConst {
  * and point as above, and
  *   count(x, y)        the history count
  *   moments(x, y, m)   the two moments */
-struct MomentPlanes {
-    const float *mom, *cnt, *guides;
-    uint32_t w;
-    VHD size_t at(int x, int y) const { return (size_t) y * w + (size_t) x; }
-    VHD void head(int x, int y, float g[4]) const {
-        const float *r = guides + 8 * at(x, y);
-        g[0] = r[0], g[1] = r[1], g[2] = r[2], g[3] = r[3];
-    }
-    VHD float view(int x, int y) const { return guides[8 * at(x, y) + 7]; }
-    VHD void point(int x, int y, float p[3]) const {
-        const float *r = guides + 8 * at(x, y) + 4;
-        p[0] = r[0], p[1] = r[1], p[2] = r[2];
-    }
-    VHD float count(int x, int y) const { return cnt[at(x, y)]; }
-    VHD void moments(int x, int y, float m[2]) const {
+struct MomentPlanes : GuidePlanes {
+    const float *mom, *cnt;
+    PP_HD float count(int x, int y) const { return cnt[at(x, y)]; }
+    PP_HD void moments(int x, int y, float m[2]) const {
         const float *r = mom + 2 * at(x, y);
         m[0] = r[0], m[1] = r[1];
     }
 };
 
 /* whether pixel (x, y) takes the 7 x 7 window: a usable pixel whose history is shorter than min_history */
-template <class Src> VHD bool variance_takes_window(const Src &S, int x, int y, const VarianceConst &K) {
+template <class Src> PP_HD bool variance_takes_window(const Src &S, int x, int y, const VarianceConst &K) {
     const float n = S.count(x, y);
     float m[2];
     S.moments(x, y, m);
-    return n >= 1.f && dn_finite(m[0]) && dn_finite(m[1]) && !(n >= K.min_history);
+    return n >= 1.f && pp_finite(m[0]) && pp_finite(m[1]) && !(n >= K.min_history);
 }
 
 /* the variance of the accumulated luminance of pixel (x, y) of a w x h image */
-template <class Src> VHD float variance_pixel(const Src &S, int x, int y, int w, int h, const VarianceConst &K) {
+template <class Src> PP_HD float variance_pixel(const Src &S, int x, int y, int w, int h, const VarianceConst &K) {
     const float n = S.count(x, y);
     float m[2];
     S.moments(x, y, m);
-    if (!(n >= 1.f) || !dn_finite(m[0]) || !dn_finite(m[1])) return 0.f;
+    if (!(n >= 1.f) || !pp_finite(m[0]) || !pp_finite(m[1])) return 0.f;
     const float tv = vr_max0(m[1] - m[0] * m[0]);
     float v = tv;
     if (!(n >= K.min_history)) {
@@ -114,13 +83,9 @@ template <class Src> VHD float variance_pixel(const Src &S, int x, int y, int w,
                 if (!(S.count(qx, qy) >= 1.f)) continue;
                 float mq[2];
                 S.moments(qx, qy, mq);
-                if (!dn_finite(mq[0]) || !dn_finite(mq[1])) continue;
+                if (!pp_finite(mq[0]) || !pp_finite(mq[1])) continue;
                 float wgt = 1.f;
-                if (hit) {
-                    float pq[3];
-                    S.point(qx, qy, pq);
-                    wgt = vr_guide_weight(g0, p0, g, pq, K.inv_sp, K.squarings);
-                }
+                if (hit) wgt = pp_guide_weight<true>(S, qx, qy, g0, p0, g, K.inv_sp, K.squarings);
                 s1 = s1 + wgt * mq[0];
                 s2 = s2 + wgt * mq[1];
                 sw = sw + wgt;
@@ -149,32 +114,21 @@ struct VarianceStep {
 };
 
 /* planes in memory, row-major: image h x w x channels, variance h x w, guides h x w x 8 */
-struct VariancePlanes {
-    const float *image, *variance, *guides;
-    uint32_t channels, w;
-    VHD size_t at(int x, int y) const { return (size_t) y * w + (size_t) x; }
-    VHD void head(int x, int y, float g[4]) const {
-        const float *r = guides + 8 * at(x, y);
-        g[0] = r[0], g[1] = r[1], g[2] = r[2], g[3] = r[3];
-    }
-    VHD float view(int x, int y) const { return guides[8 * at(x, y) + 7]; }
-    VHD void point(int x, int y, float p[3]) const {
-        const float *r = guides + 8 * at(x, y) + 4;
-        p[0] = r[0], p[1] = r[1], p[2] = r[2];
-    }
-    VHD void color(int x, int y, float c[3]) const {
+struct VariancePlanes : GuidePlanes {
+    const float *image, *variance;
+    uint32_t channels;
+    PP_HD void color(int x, int y, float c[3]) const {
         const float *r = image + channels * at(x, y);
         c[0] = r[0], c[1] = r[1], c[2] = r[2];
     }
-    VHD float var(int x, int y) const { return variance[at(x, y)]; }
-    VHD float shape(int x, int y) const { return guides[8 * at(x, y)]; }
+    PP_HD float var(int x, int y) const { return variance[at(x, y)]; }
 };
 
 /* gk = {1/4, 1/2, 1/4} at i = -1 .. 1 */
-VHD float vr_gk(int i) { return i == 0 ? 0.5f : 0.25f; }
+PP_HD float vr_gk(int i) { return i == 0 ? 0.5f : 0.25f; }
 
 /* gv of pixel (x, y), whose shape and view are shape0 and v0: the 3 x 3 prefilter of the input variance at step 1 */
-template <class Pre> VHD float variance_prefilter(const Pre &S, int x, int y, int w, int h, float shape0, float v0) {
+template <class Pre> PP_HD float variance_prefilter(const Pre &S, int x, int y, int w, int h, float shape0, float v0) {
     float sg = 0.f, sk = 0.f;
 #pragma unroll
     for (int dy = -1; dy <= 1; ++dy) {
@@ -186,7 +140,7 @@ template <class Pre> VHD float variance_prefilter(const Pre &S, int x, int y, in
             if (qx < 0 || qx >= w) continue;
             if (S.shape(qx, qy) != shape0 || S.view(qx, qy) != v0) continue;
             const float vq = S.var(qx, qy);
-            if (!dn_finite(vq)) continue;
+            if (!pp_finite(vq)) continue;
             const float kw = vr_gk(dy) * vr_gk(dx);
             sg = sg + kw * vq;
             sk = sk + kw;
@@ -198,7 +152,7 @@ template <class Pre> VHD float variance_prefilter(const Pre &S, int x, int y, in
 /* out = the filtered RGB of pixel (x, y) of a w x h image and vout its filtered variance: one iteration.  S serves the
  * 25 taps, P the prefilter */
 template <class Src, class Pre>
-VHD void denoise_variance_pixel(const Src &S, const Pre &P, int x, int y, int w, int h, const VarianceStep &K, float out[3],
+PP_HD void denoise_variance_pixel(const Src &S, const Pre &P, int x, int y, int w, int h, const VarianceStep &K, float out[3],
                                 float &vout) {
     float g0[4], c[3], p0[3] = {0.f, 0.f, 0.f};
     S.head(x, y, g0);
@@ -207,7 +161,7 @@ VHD void denoise_variance_pixel(const Src &S, const Pre &P, int x, int y, int w,
     const bool hit = g0[0] >= 0.f;
     if (hit) S.point(x, y, p0);
     const float gv = variance_prefilter(P, x, y, w, h, g0[0], v0);
-    const float lp = vr_lum(c);
+    const float lp = pp_lum(c);
     const float kl = 1.f / (K.sl2 * gv + K.var_floor);
     float sum[3] = {0.f, 0.f, 0.f}, sum_w = 0.f, sum_v = 0.f;
     for (int dy = -2; dy <= 2; ++dy) {
@@ -222,17 +176,13 @@ VHD void denoise_variance_pixel(const Src &S, const Pre &P, int x, int y, int w,
             if (g[0] != g0[0] || S.view(qx, qy) != v0) continue;   /* another shape (or hit against miss), another view */
             float cq[3];
             S.color(qx, qy, cq);
-            if (!dn_finite(cq[0]) || !dn_finite(cq[1]) || !dn_finite(cq[2])) continue;
+            if (!pp_finite(cq[0]) || !pp_finite(cq[1]) || !pp_finite(cq[2])) continue;
             const float vq = S.var(qx, qy);
-            if (!dn_finite(vq)) continue;
-            const float dl = vr_lum(cq) - lp;
+            if (!pp_finite(vq)) continue;
+            const float dl = pp_lum(cq) - lp;
             const float wl = 1.f / (1.f + (dl * dl) * kl);
-            float wgt = (dn_hk(dy) * dn_hk(dx)) * wl;
-            if (hit) {
-                float pq[3];
-                S.point(qx, qy, pq);
-                wgt = wgt * vr_guide_weight(g0, p0, g, pq, K.inv_sp, K.squarings);
-            }
+            float wgt = (pp_hk(dy) * pp_hk(dx)) * wl;
+            if (hit) wgt = wgt * pp_guide_weight<true>(S, qx, qy, g0, p0, g, K.inv_sp, K.squarings);
             sum[0] = sum[0] + wgt * cq[0];
             sum[1] = sum[1] + wgt * cq[1];
             sum[2] = sum[2] + wgt * cq[2];
@@ -246,7 +196,5 @@ VHD void denoise_variance_pixel(const Src &S, const Pre &P, int x, int y, int w,
     out[2] = ok ? sum[2] / sum_w : c[2];
     vout = ok ? sum_v / (sum_w * sum_w) : S.var(x, y);
 }
-
-#undef VHD
 
 } // namespace amvpt

@@ -7,6 +7,7 @@
  * gives the ViewBuf back.  Calls on several streams never share one in flight.  Limits (also in the headers): the pool
  * does not shrink -- it holds as many ViewBufs as calls were ever enqueued at once, whole 4 KiB of each memory and one
  * event apiece -- and a call that has to allocate cannot be captured into a graph.
+ * view_buf_launch is that whole sequence around a caller's fill and launch.
  * Every unit that includes this has a pool of its own (the state below is static): the units share the code, no state.
  * `who` is the entry's name, the first word of every message.
  */
@@ -71,6 +72,21 @@ static hipError_t view_buf_give(const ViewBuf &b, hipStream_t st) {
     std::lock_guard<std::mutex> lock(g_view_mutex);
     g_view_bufs.push_back(b);
     return e;
+}
+
+/* a call's device half: fill(host block) writes the `bytes` of its table, which go up on `st`; launch(device block)
+ * enqueues the kernel behind them and returns hipGetLastError(); the ViewBuf goes back behind that either way */
+template <class Fill, class Launch>
+static amvpt_status view_buf_launch(const std::string &who, size_t bytes, hipStream_t st, Fill fill, Launch launch) {
+    ViewBuf vb;
+    if (amvpt_status rc = view_buf_take(who, bytes, vb)) return rc;
+    fill(vb.host);
+    hipError_t e = hipMemcpyAsync(vb.p, vb.host, bytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = launch((const void *) vb.p);
+    const hipError_t eg = view_buf_give(vb, st);
+    if (e != hipSuccess) return hip_fail((who + " launch").c_str(), (int) e);
+    if (eg != hipSuccess) return hip_fail((who + " hipEventRecord").c_str(), (int) eg);
+    return AMVPT_OK;
 }
 
 } // namespace amvpt
