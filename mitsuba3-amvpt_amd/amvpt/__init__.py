@@ -176,6 +176,40 @@ class SynthParams(ctypes.Structure):
         return "SynthParams(plane_tol=%r, normal_cos=%r, view_falloff=%r, fill_iterations=%r)" % self.values()
 
 
+TONEMAP_LINEAR, TONEMAP_REINHARD, TONEMAP_ACES = range(3)
+TONEMAP_OPS = {"linear": TONEMAP_LINEAR, "reinhard": TONEMAP_REINHARD, "aces": TONEMAP_ACES}
+
+
+class TonemapParams(ctypes.Structure):
+    """amvpt_tonemap_params (include/amvpt_tonemap.h).  Without arguments: amvpt_tonemap_default_params' values,
+    the identity (LINEAR, no metering, ev 0, key 0.18).  `op` is a TONEMAP_* value or its lower-case name."""
+    _fields_ = [("op", u32), ("auto_exposure", u32), ("ev", f32), ("key", f32), ("lo", f32), ("hi", f32), ("adapt", f32),
+                ("white", f32), ("min_ev", f32), ("max_ev", f32)]
+
+    def __init__(self, op=TONEMAP_LINEAR, auto_exposure=False, ev=0.0, key=0.18, lo=0.10, hi=0.95, adapt=1.0, white=4.0,
+                 min_ev=-16.0, max_ev=16.0):
+        super().__init__(TONEMAP_OPS[op] if isinstance(op, str) else op, int(auto_exposure), ev, key, lo, hi, adapt, white,
+                         min_ev, max_ev)
+
+    def values(self):
+        return (self.op, self.auto_exposure, self.ev, self.key, self.lo, self.hi, self.adapt, self.white, self.min_ev,
+                self.max_ev)
+
+    def __repr__(self):
+        return ("TonemapParams(op=%r, auto_exposure=%r, ev=%r, key=%r, lo=%r, hi=%r, adapt=%r, white=%r, min_ev=%r, "
+                "max_ev=%r)" % self.values())
+
+
+class TonemapState(ctypes.Structure):
+    """amvpt_tonemap_state (include/amvpt_tonemap.h): the histogram of the last metered frame and the exposure it left.
+    A zero-filled one (TonemapState()) is fresh."""
+    _fields_ = [("hist", u32 * 512), ("counted", u32), ("skipped", u32), ("frames", u32), ("exposure", f32),
+                ("log2_exposure", f64)]
+
+    def histogram(self):
+        return np.frombuffer(self, dtype=np.uint32, count=512).copy()
+
+
 # amvpt_run_exchange_fn: (ctx, n_runs, *run_lane_begin, *run_count, *run_prefix, *total) -> 0 on success
 RunExchangeFn = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, u32, ctypes.POINTER(u64), ctypes.POINTER(u64),
                                  ctypes.POINTER(u64), ctypes.POINTER(u64))
@@ -342,6 +376,22 @@ def hip_lib():
             fill = [vp, u32, u32, u32, vp, vp, sq, vp, vp, vp, vp]
             for fn, args in (("amvpt_synth", planes + [vp]), ("amvpt_synth_host", planes),
                              ("amvpt_synth_fill", fill + [vp]), ("amvpt_synth_fill_host", fill)):
+                getattr(L, fn).restype = ctypes.c_int
+                getattr(L, fn).argtypes = args
+        if hasattr(L, "amvpt_tonemap_version"):   # include/amvpt_tonemap.h
+            vp = ctypes.c_void_p
+            tq, rc = ctypes.POINTER(TonemapParams), ctypes.POINTER(u32 * 4)
+            L.amvpt_tonemap_version.restype = u32
+            L.amvpt_tonemap_default_params.restype = TonemapParams
+            L.amvpt_tonemap_default_params.argtypes = []
+            L.amvpt_tonemap_exp2_host.restype = f64
+            L.amvpt_tonemap_exp2_host.argtypes = [f64]
+            for fn, args in (("amvpt_tonemap_meter", [vp, u32, u32, u32, rc, tq, vp, vp]),
+                             ("amvpt_tonemap_meter_host", [vp, u32, u32, u32, rc, tq, vp]),
+                             ("amvpt_tonemap_apply", [vp, u32, u32, u32, tq, vp, vp, vp]),
+                             ("amvpt_tonemap_apply_host", [vp, u32, u32, u32, tq, vp, vp]),
+                             ("amvpt_tonemap_srgb8", [vp, u32, u32, u32, tq, vp, vp, vp]),
+                             ("amvpt_tonemap_srgb8_host", [vp, u32, u32, u32, tq, vp, vp])):
                 getattr(L, fn).restype = ctypes.c_int
                 getattr(L, fn).argtypes = args
         _hip = L
@@ -635,6 +685,94 @@ def synth_fill_host(image, cover, guides, sp=None):
                                    scratch.ctypes.data if scratch is not None else None, cout.ctypes.data,
                                    cscratch.ctypes.data if cscratch is not None else None), L)
     return out, cout
+
+
+def tonemap_version():
+    """AMVPT_TONEMAP_VERSION of the loaded library (include/amvpt_tonemap.h)."""
+    return hip_lib().amvpt_tonemap_version()
+
+
+def tonemap_default_params():
+    """amvpt_tonemap_default_params of the loaded library."""
+    c = hip_lib().amvpt_tonemap_default_params()
+    return TonemapParams(*c.values())
+
+
+def tonemap_exp2_host(x):
+    """exp2_pm of include/amvpt_tonemap.h at the float64 x (amvpt_tonemap_exp2_host)."""
+    return hip_lib().amvpt_tonemap_exp2_host(float(x))
+
+
+def _tonemap_image(who, image):
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    if img.ndim != 3:
+        raise ValueError("%s: an (H, W, C) image is needed" % who)
+    return img
+
+
+def tonemap_meter_device(image_ptr, channels, width, height, state_ptr, params=None, rect=None, stream=None):
+    """amvpt_tonemap_meter over device pointers, ordered on `stream`: the histogram of the image (`rect` = (x0, y0, w,
+    h) in pixels; None: all of it) and the exposure it gives, into the amvpt_tonemap_state at state_ptr."""
+    L = hip_lib()
+    q = params if params is not None else tonemap_default_params()
+    _check(L.amvpt_tonemap_meter(ctypes.c_void_p(image_ptr), channels, width, height, _rect_ref(rect), ctypes.byref(q),
+                                 ctypes.c_void_p(state_ptr), ctypes.c_void_p(stream or 0)), L)
+
+
+def tonemap_device(image_ptr, channels, width, height, out_ptr, params=None, state_ptr=None, stream=None):
+    """amvpt_tonemap_apply over device pointers, ordered on `stream`: height x width x channels float32 at out_ptr, which
+    may be image_ptr itself.  state_ptr may be None unless params.auto_exposure is set."""
+    L = hip_lib()
+    q = params if params is not None else tonemap_default_params()
+    _check(L.amvpt_tonemap_apply(ctypes.c_void_p(image_ptr), channels, width, height, ctypes.byref(q),
+                                 ctypes.c_void_p(state_ptr or 0), ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream or 0)), L)
+
+
+def tonemap_srgb8_device(image_ptr, channels, width, height, out_ptr, params=None, state_ptr=None, stream=None):
+    """amvpt_tonemap_srgb8 over device pointers, ordered on `stream`: height x width x 3 uint8 at out_ptr."""
+    L = hip_lib()
+    q = params if params is not None else tonemap_default_params()
+    _check(L.amvpt_tonemap_srgb8(ctypes.c_void_p(image_ptr), channels, width, height, ctypes.byref(q),
+                                 ctypes.c_void_p(state_ptr or 0), ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream or 0)), L)
+
+
+def tonemap_meter_host(image, params=None, state=None, rect=None):
+    """amvpt_tonemap_meter_host over numpy: meters the (H, W, 3 or 4) float32 image into `state` (a TonemapState, updated
+    in place; None: a fresh one) and returns it.  Bit-identical to the device entry; needs no device."""
+    L = hip_lib()
+    img = _tonemap_image("tonemap_meter_host", image)
+    q = params if params is not None else tonemap_default_params()
+    s = state if state is not None else TonemapState()
+    h, w, c = img.shape
+    _check(L.amvpt_tonemap_meter_host(img.ctypes.data, c, w, h, _rect_ref(rect), ctypes.byref(q), ctypes.addressof(s)), L)
+    return s
+
+
+def tonemap_host(image, params=None, state=None, in_place=False):
+    """amvpt_tonemap_apply_host over numpy: (H, W, 3 or 4) float32 -> the mapped floats, alpha passed through.
+    in_place=True maps a contiguous float32 `image` onto itself and returns it."""
+    L = hip_lib()
+    img = _tonemap_image("tonemap_host", image)
+    if in_place and img is not image:
+        raise ValueError("tonemap_host: in_place needs a contiguous float32 array")
+    q = params if params is not None else tonemap_default_params()
+    out = img if in_place else np.empty_like(img)
+    h, w, c = img.shape
+    _check(L.amvpt_tonemap_apply_host(img.ctypes.data, c, w, h, ctypes.byref(q),
+                                      ctypes.addressof(state) if state is not None else None, out.ctypes.data), L)
+    return out
+
+
+def tonemap_srgb8_host(image, params=None, state=None):
+    """amvpt_tonemap_srgb8_host over numpy: (H, W, 3 or 4) float32 -> (H, W, 3) uint8 sRGB of the mapped colours."""
+    L = hip_lib()
+    img = _tonemap_image("tonemap_srgb8_host", image)
+    q = params if params is not None else tonemap_default_params()
+    h, w, c = img.shape
+    out = np.empty((h, w, 3), dtype=np.uint8)
+    _check(L.amvpt_tonemap_srgb8_host(img.ctypes.data, c, w, h, ctypes.byref(q),
+                                      ctypes.addressof(state) if state is not None else None, out.ctypes.data), L)
+    return out
 
 
 def guides_version():
@@ -1465,3 +1603,70 @@ class ViewSynthesizer:
             self.holes = int((cover == 0).sum().item())
         self.source_image, self.source_guides, self.image, self.cover = src_image, src_guides, img, cover
         return img, cover
+
+
+class ToneMapper:
+    """The tone-mapping stage over torch device tensors (include/amvpt_tonemap.h).  It owns the amvpt_tonemap_state in
+    device memory; with params.auto_exposure set, `run` and `run_float` meter the frame into it first, and the exposure
+    adapts from call to call.  Nothing returns to the host between metering and tone mapping.  The input of the last
+    run stays reachable as `frame`."""
+
+    def __init__(self, params=None):
+        self.params = params if params is not None else tonemap_default_params()
+        self._state = None
+        self.frame = None     # the input of the last run, which stays reachable
+        self._device = None   # (Scene, DeviceScene) of device_scene_for
+
+    def device_scene_for(self, scene, scene_desc):
+        """The DeviceScene this tone mapper keeps for the loaded `scene` (amvpt.display.display(..., tonemap=) with
+        neither an accumulator nor a synthesizer): created from `scene_desc` at the first call."""
+        if self._device is None or self._device[0] is not scene:
+            self._device = (scene, DeviceScene(scene_desc))
+        return self._device[1]
+
+    def _state_tensor(self):
+        import torch
+        if self._state is None:
+            self._state = torch.zeros(ctypes.sizeof(TonemapState), dtype=torch.uint8, device="cuda")
+        return self._state
+
+    def reset(self):
+        """Return the state to a fresh one: the next metered frame sets the exposure without adaptation."""
+        if self._state is not None:
+            self._state.zero_()
+
+    def state(self):
+        """The state struct, downloaded (synchronises with the work issued so far)."""
+        return TonemapState.from_buffer_copy(self._state_tensor().cpu().numpy().tobytes())
+
+    def _frame(self, who, frame):
+        import torch
+        if (not hasattr(frame, "data_ptr") or frame.dtype != torch.float32 or not frame.is_contiguous() or frame.dim() != 3):
+            raise ValueError("ToneMapper.%s: a contiguous float32 (H, W, C) device tensor is needed" % who)
+        return int(frame.shape[0]), int(frame.shape[1]), int(frame.shape[2])
+
+    def _run(self, who, frame, stream, rect, out_of, entry):
+        import torch
+        h, w, c = self._frame(who, frame)
+        st = torch.cuda.current_stream() if not stream else torch.cuda.ExternalStream(int(stream))
+        with torch.cuda.stream(st):
+            state = self._state_tensor().data_ptr() if self.params.auto_exposure else None
+            if state is not None:
+                tonemap_meter_device(frame.data_ptr(), c, w, h, state, self.params, rect=rect, stream=st.cuda_stream)
+            out = out_of(h, w, c)
+            entry(frame.data_ptr(), c, w, h, out.data_ptr(), self.params, state_ptr=state, stream=st.cuda_stream)
+        self.frame = frame
+        return out
+
+    def run(self, frame, stream=None, rect=None):
+        """Meter `frame` (with auto_exposure; `rect` = (x0, y0, w, h) restricts the metering) and map it to 8-bit sRGB
+        (amvpt_tonemap_srgb8), ordered on `stream` (a hipStream_t handle; None: torch's current stream) -> a new
+        (H, W, 3) uint8 device tensor."""
+        import torch
+        return self._run("run", frame, stream, rect,
+                         lambda h, w, c: torch.empty((h, w, 3), dtype=torch.uint8, device="cuda"), tonemap_srgb8_device)
+
+    def run_float(self, frame, stream=None, rect=None):
+        """`run` with float output (amvpt_tonemap_apply) -> a new (H, W, C) float32 device tensor."""
+        import torch
+        return self._run("run_float", frame, stream, rect, lambda h, w, c: torch.empty_like(frame), tonemap_device)

@@ -5,7 +5,8 @@ src/mitsuba/program.cpp:199-276 with the presets of src/mitsuba/preset.h).
 
 `srgb8`, `interlace` and `views` run the host entries over numpy arrays and need no device;
 `srgb8_device` / `interlace_device` launch the kernels over device pointers; `display` renders a scene and
-runs the whole stage on the device, downloading the display image once.  `depth_quilt` is the 8-bit depth
+runs the whole stage on the device, downloading the display image once (with `tonemap=` an amvpt.ToneMapper,
+include/amvpt_tonemap.h, stands where the sRGB conversion does).  `depth_quilt` is the 8-bit depth
 quilt of a scene (include/amvpt_guides.h), the RGB-D companion of the sRGB quilt.
 """
 import ctypes
@@ -163,7 +164,7 @@ def preset_for_scene(scene, sensor=0):
 
 
 def display(scene, preset=None, size=(1280, 720), quilt=False, nearest=False, sensor=0, seed=0, spp=0,
-            counters=None, stream=None, rerender=True, denoise=None, temporal=None, synth=None):
+            counters=None, stream=None, rerender=True, denoise=None, tonemap=None, temporal=None, synth=None):
     """Render `scene` and run the display stage on the device (amvpt_host_display): render -> develop -> sRGB
     quilt -> lenticular image, one download -> (size[1], size[0], 3) uint8.  preset None: preset_for_scene.
     rerender=False runs the stage alone on the developed frame the last render / display of this sensor left on
@@ -180,15 +181,24 @@ def display(scene, preset=None, size=(1280, 720), quilt=False, nearest=False, se
     synth None: the rendered quilt is the one shown, and the call and its bytes are what they are without the keyword.
     An amvpt.ViewSynthesizer makes the dense quilt of its own scene from the rendered one (include/amvpt_synth.h) after
     the accumulator and the denoiser (_display_synth): render -> develop -> (temporal) -> (denoise) -> synthesis -> sRGB
-    quilt -> lenticular image, and preset None is preset_for_scene of the synthesizer's scene."""
+    quilt -> lenticular image, and preset None is preset_for_scene of the synthesizer's scene.
+    tonemap None: the sRGB quilt clips at 1, and the call and its bytes are what they are without the keyword.  An
+    amvpt.ToneMapper takes the place of the sRGB conversion at the end of the chain (include/amvpt_tonemap.h): the frame
+    is metered where its parameters ask for it, scaled by one exposure for the whole quilt, mapped by the operator and
+    written as sRGB bytes in one pass, after the accumulator, the denoiser and the synthesis where they are given, and
+    over torch device tensors without them (_display_tonemap).  It needs a fresh frame, as the accumulator does."""
     if isinstance(denoise, amvpt.VarianceParams) and (temporal is None or not temporal.with_moments):
         raise ValueError("display: a VarianceParams denoiser needs temporal=TemporalAccumulator(moments=True)")
+    if tonemap is not None and not rerender:
+        raise ValueError("display: tone mapping needs a fresh frame (rerender=True)")
     if synth is not None:
         return _display_synth(scene, synth, temporal, preset, size, quilt, nearest, sensor, seed, spp, counters, stream,
-                              rerender, denoise)
+                              rerender, denoise, tonemap)
     if temporal is not None:
         return _display_temporal(scene, temporal, preset, size, quilt, nearest, sensor, seed, spp, counters, stream,
-                                 rerender, denoise)
+                                 rerender, denoise, tonemap)
+    if tonemap is not None:
+        return _display_tonemap(scene, tonemap, preset, size, quilt, nearest, sensor, seed, spp, counters, stream, denoise)
     _, H = _libs()
     if denoise is not None and denoise is not False:
         if rerender:
@@ -213,7 +223,54 @@ def display(scene, preset=None, size=(1280, 720), quilt=False, nearest=False, se
     return out
 
 
-def _display_temporal(scene, acc, preset, size, quilt, nearest, sensor, seed, spp, counters, stream, rerender, denoise):
+def _quilt8(frame, c, w, h, tonemap, stream):
+    """The 8-bit sRGB quilt of the float frame (a torch device tensor), the step the torch chains share: srgb8_device, or
+    the tone mapper's metered and fused form in its place."""
+    import torch
+    if tonemap is not None:
+        return tonemap.run(frame, stream=stream)
+    q8 = torch.empty((h, w, 3), dtype=torch.uint8, device="cuda")
+    srgb8_device(frame.data_ptr(), c, w, h, q8.data_ptr(), stream=stream)
+    return q8
+
+
+def _display_tonemap(scene, tonemap, preset, size, quilt, nearest, sensor, seed, spp, counters, stream, denoise):
+    """display with a ToneMapper and neither an accumulator nor a synthesizer: render -> develop -> (denoiser) -> meter,
+    tone map and sRGB -> lenticular image over torch device tensors, downloaded once.  The device scene is one the tone
+    mapper keeps; the frame the host library caches for rerender=False is not touched."""
+    import torch
+    L, _ = _libs()
+    sd, vd, p = scene.describe(sensor, seed, spp)
+    dev = tonemap.device_scene_for(scene, sd)
+    h, w = int(p.film_height), int(p.film_width)
+    c = 4 if p.film_alpha else 3
+    st = torch.cuda.current_stream() if not stream else torch.cuda.ExternalStream(int(stream))
+    with torch.cuda.stream(st):
+        film = torch.zeros((h, w, c + 1), dtype=torch.float32, device="cuda")
+        frame = torch.empty((h, w, c), dtype=torch.float32, device="cuda")
+        dev.render(vd, p, film.data_ptr(), stream=st.cuda_stream, counters=counters)
+        _check_hip(L.amvpt_develop(ctypes.c_void_p(film.data_ptr()), ctypes.c_void_p(frame.data_ptr()), w, h, p.film_alpha,
+                                   ctypes.c_void_p(st.cuda_stream)), L)
+        if denoise is not None and denoise is not False:
+            guides = torch.empty((h, w, 8), dtype=torch.float32, device="cuda")
+            dev.guides(vd, p, guides.data_ptr(), stream=st.cuda_stream)
+            q = denoise if isinstance(denoise, amvpt.DenoiseParams) else amvpt.DenoiseParams(
+                sigma_plane=amvpt.denoise_sigma_plane(guides.cpu().numpy()))
+            out, scratch = torch.empty_like(frame), torch.empty_like(frame)
+            amvpt.denoise_device(frame.data_ptr(), c, w, h, guides.data_ptr(), out.data_ptr(), scratch.data_ptr(), q,
+                                 stream=st.cuda_stream)
+            frame = out
+        q8 = _quilt8(frame, c, w, h, tonemap, st.cuda_stream)
+        dw, dh = int(size[0]), int(size[1])
+        shown = torch.empty((max(dh, 0), max(dw, 0), 3), dtype=torch.uint8, device="cuda")
+        interlace_device(q8.data_ptr(), w, h, 3, shown.data_ptr(), (dw, dh), preset if preset is not None else
+                         preset_for_scene(scene, sensor), quilt=quilt, nearest=nearest, stream=st.cuda_stream)
+        st.synchronize()
+        return shown.cpu().numpy()
+
+
+def _display_temporal(scene, acc, preset, size, quilt, nearest, sensor, seed, spp, counters, stream, rerender, denoise,
+                      tonemap=None):
     """display with a TemporalAccumulator: render -> develop -> temporal accumulation -> (denoiser) -> sRGB quilt ->
     lenticular image over torch device tensors; the display image is downloaded once (denoise=True also downloads
     the guide records, for denoise_sigma_plane; a DenoiseParams does not; a VarianceParams runs the accumulator's own
@@ -245,8 +302,7 @@ def _display_temporal(scene, acc, preset, size, quilt, nearest, sensor, seed, sp
             amvpt.denoise_device(frame.data_ptr(), c, w, h, acc.guides.data_ptr(), out.data_ptr(), scratch.data_ptr(), q,
                                  stream=st.cuda_stream)
             frame = out
-        q8 = torch.empty((h, w, 3), dtype=torch.uint8, device="cuda")
-        srgb8_device(frame.data_ptr(), c, w, h, q8.data_ptr(), stream=st.cuda_stream)
+        q8 = _quilt8(frame, c, w, h, tonemap, st.cuda_stream)
         dw, dh = int(size[0]), int(size[1])
         shown = torch.empty((max(dh, 0), max(dw, 0), 3), dtype=torch.uint8, device="cuda")
         interlace_device(q8.data_ptr(), w, h, 3, shown.data_ptr(), (dw, dh), preset if preset is not None else
@@ -255,7 +311,8 @@ def _display_temporal(scene, acc, preset, size, quilt, nearest, sensor, seed, sp
         return shown.cpu().numpy()
 
 
-def _display_synth(scene, synth, acc, preset, size, quilt, nearest, sensor, seed, spp, counters, stream, rerender, denoise):
+def _display_synth(scene, synth, acc, preset, size, quilt, nearest, sensor, seed, spp, counters, stream, rerender, denoise,
+                   tonemap=None):
     """display with a ViewSynthesizer, with or without a TemporalAccumulator: _display_temporal's chain over torch
     device tensors with the synthesis between the denoiser and the sRGB quilt; what is shown is the synthesizer's dense
     quilt.  The device scene is the accumulator's where there is one, else one the synthesizer keeps."""
@@ -290,8 +347,7 @@ def _display_synth(scene, synth, acc, preset, size, quilt, nearest, sensor, seed
             frame = out
         dense, _ = synth.run(dev, vd, p, frame, guides, stream=st.cuda_stream)
         qh, qw = int(dense.shape[0]), int(dense.shape[1])
-        q8 = torch.empty((qh, qw, 3), dtype=torch.uint8, device="cuda")
-        srgb8_device(dense.data_ptr(), c, qw, qh, q8.data_ptr(), stream=st.cuda_stream)
+        q8 = _quilt8(dense, c, qw, qh, tonemap, st.cuda_stream)
         dw, dh = int(size[0]), int(size[1])
         shown = torch.empty((max(dh, 0), max(dw, 0), 3), dtype=torch.uint8, device="cuda")
         interlace_device(q8.data_ptr(), qw, qh, 3, shown.data_ptr(), (dw, dh), preset if preset is not None else

@@ -119,4 +119,22 @@ DHD uint8_t interlace_value(const uint8_t *src, const DisplayParams &P, uint32_t
 
 #undef DHD
 
+/* device only, for the kernels that write RGB bytes (amvpt_display.hip, amvpt_tonemap.hip) */
+static __device__ __forceinline__ uint32_t pack4(uint8_t a, uint8_t b, uint8_t c, uint8_t d) {
+    return (uint32_t) a | ((uint32_t) b << 8) | ((uint32_t) c << 16) | ((uint32_t) d << 24);
+}
+
+/* 12 bytes at out (the bytes of four RGB pixels): three dword stores, or byte stores */
+template <bool kDword> static __device__ __forceinline__ void store12(uint8_t *out, const uint8_t *v) {
+    if (kDword) {
+        uint32_t *o = reinterpret_cast<uint32_t *>(out);
+        o[0] = pack4(v[0], v[1], v[2], v[3]);
+        o[1] = pack4(v[4], v[5], v[6], v[7]);
+        o[2] = pack4(v[8], v[9], v[10], v[11]);
+    } else {
+#pragma unroll
+        for (uint32_t i = 0; i < 12; ++i) out[i] = v[i];
+    }
+}
+
 } // namespace amvpt

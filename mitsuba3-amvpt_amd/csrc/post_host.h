@@ -1,6 +1,6 @@
 /*
  * post_host.h -- the host side the post-process units share (amvpt_display.hip, amvpt_guides.hip, amvpt_denoise.hip,
- * amvpt_temporal.hip, amvpt_variance.hip, amvpt_synth.hip): the device test, and the refusals that are the same from
+ * amvpt_temporal.hip, amvpt_variance.hip, amvpt_synth.hip, amvpt_tonemap.hip): the device test, and the refusals that are the same from
  * entry to entry, each worded once (post_host.cpp).  A unit keeps its own null tests and parameter ranges and calls
  * these between them; the order decides which of two faults a call hears of.  The upload of a view table is viewbuf.h's,
  * beside the pool it draws on.
